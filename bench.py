@@ -11,6 +11,12 @@ over ranks (independent units, weak scaling).
 
     python bench.py [--gpus N --steps K --warmup W --config c2|c3|c4|c5 --reports R --prefixes P]
     (N > 1: launched by torch.distributed.run, one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--full adds every other leg after the timed steps (standalone-sponge pass,
+full job, CPU baselines and parity, the sweeps' plaintext check and
+spec-literal rate, the north_star job); --dump-outputs DIR writes what the
+last timed step returned as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -72,7 +78,7 @@ CONFIGS = {
 }
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
@@ -117,7 +123,44 @@ def parse():
                          "kernel's own rooflines; 0 skips it")
     ap.add_argument("--north-star-reports", type=int, default=0,
                     help="job size of the north_star leg (0 = the 1M of BASELINE.json; smaller only for rehearsals)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: the standalone-sponge pass, the full job, "
+                         "the CPU baselines and their parity checks, the sweeps' plaintext check and spec-literal "
+                         "rate, the north_star job (each still has its own switch above); without it a run sets "
+                         "up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    args = ap.parse_args(argv)
+    if not args.full:
+        args.standalone = args.cpu_baseline = args.north_star = args.full_job = 0
+    return args
+
+
+# ---------------------------------------------------------------- --dump-outputs
+DUMP_BUDGET = 60 * 10 ** 6  # bytes over all files of one --dump-outputs (the limit is 64 MB)
+
+
+def limbs(raw, enc):
+    """encode_vec bytes -> float64 [elements, enc / 4]: each field element as
+    its little-endian 32-bit limbs (exact in float64; a whole Field64 element
+    is not)."""
+    return np.frombuffer(raw, dtype="<u4").astype(np.float64).reshape(-1, enc // 4)
+
+
+def dump_outputs(dirname, arrays):
+    """Write {name: 2-D array} as dirname/<name>.npy.  Each array gets an
+    equal share of DUMP_BUDGET; a larger one is cut to a fixed, seeded sample
+    of its rows (the same rows in every run with the same arguments)."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET // max(len(arrays), 1)
+    for (name, a) in arrays.items():
+        assert a.dtype in (np.float32, np.float64) and a.ndim == 2
+        row = max(a.shape[1] * a.itemsize, 1)
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0x4D41).choice(a.shape[0], size=max(share // row, 1), replace=False))
+            a = a[keep]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
 
 
 def _attrs(rng, bits, n_prefixes):
@@ -586,6 +629,15 @@ def run_sweep(args, cfg, world, rank, local, dist, torch, split=None, steps=None
     (free_b, total_b) = torch.cuda.mem_get_info()
     hbm_used = (total_b - free_b) / 1e9  # whole device, arena and frontier cache included
     dt = max_over_ranks(dist, torch, dt)
+    if args.dump_outputs and rank == 0 and emit and cfg["circuit"] in ("Count", "Sum"):
+        # the last timed sweep's heavy hitters (one row of bits each) and every level's
+        # candidate count and per-candidate aggregate (integers far below 2^53)
+        last = traces[-1]
+        dump_outputs(args.dump_outputs, {
+            "heavy_hitters": np.array(hh, dtype=np.float32).reshape(len(hh), bits),
+            "level_candidates": np.array([[lv.level, len(lv.prefixes)] for lv in last], dtype=np.float64),
+            "level_agg_results": np.array([x for lv in last for x in lv.agg_result], dtype=np.float64).reshape(-1, 1),
+        })
     # the same sweep once more with every binder-sponge launch running alone
     # (results identical; its trajectory is the timed sweep's): the sponge
     # kernels' and the level kernel's own rates, beside the co-running ones
@@ -608,7 +660,7 @@ def run_sweep(args, cfg, world, rank, local, dist, torch, split=None, steps=None
     # weight), and sampled levels' aggregates equal the plaintext prefix sums
     # (talks/func.py:49-80); with the job's reports on this rank
     plain_ok = None
-    if alphas_job is not None:
+    if args.full and alphas_job is not None:
         keys, inv = np.unique(alphas_job, axis=0, return_inverse=True)
         tot = np.bincount(inv.ravel(), weights=w_job)
         want = set(bytes(k) for (k, t) in zip(keys, tot) if t >= threshold)
@@ -777,7 +829,7 @@ def run_sweep(args, cfg, world, rank, local, dist, torch, split=None, steps=None
         "with_frontier_cache" if args.frontier_cache else "spec_literal": units / dt,
         "unit": "report*prefix/s (both aggregators' prep_init + decide + fold per level, whole sweep)",
     }
-    if args.frontier_cache and cfg.get("spec_sample"):
+    if args.full and args.frontier_cache and cfg.get("spec_sample"):
         # spec-literal rate: every level's prep_init evaluates
         # its whole tree, as the reference does; the same per-level body on a
         # bounded sample of the reports with the timed sweep's candidate lists
@@ -1085,8 +1137,9 @@ def main():
     t0 = time.perf_counter()
     aes_ms = proof_ms = absorb_ms = total_ms = 0.0
     n_launch = 0
+    last_out = None
     for k in range(args.steps):
-        step(slices[k % len(slices)])
+        last_out = step(slices[k % len(slices)])
         (ea, na_, ep, _np, eb, _nb, t) = m.last_timing3()
         aes_ms += ea
         proof_ms += ep
@@ -1099,6 +1152,20 @@ def main():
         dist.barrier()
     dt = time.perf_counter() - t0
     dt = max_over_ranks(dist, torch, dt)
+
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed back: the (merged) agg share it returned, and the
+        # prep shares, joint-rand seeds and per-report status its prep_init left for prep_result
+        if not isinstance(last_out, (bytes, bytearray)):  # the gloo merge returns a device tensor
+            last_out = last_out.cpu().numpy().tobytes()
+        last_reps = slices[(args.steps - 1) % len(slices)]
+        (ps, js, _o, st) = m.prep_result(last_reps, args.agg_id, enc_ap)
+        dump_outputs(args.dump_outputs, {
+            "agg_share": limbs(last_out, m.field.ENCODED_SIZE),
+            "prep_shares": np.frombuffer(ps, np.uint8).astype(np.float32).reshape(last_reps.n, -1),
+            "joint_rand_seeds": np.frombuffer(js, np.uint8).astype(np.float32).reshape(last_reps.n, 32),
+            "prep_status": st.astype(np.float32).reshape(-1, 1),
+        })
 
     alone = None
     if getattr(args, "standalone", 1):

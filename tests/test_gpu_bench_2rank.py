@@ -21,7 +21,7 @@ def test_bench_two_ranks_on_one_gpu():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     env = dict(os.environ, MASTIC_BENCH_BACKEND="gloo", MASTIC_BENCH_DEVICE="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "1", "--warmup", "1",
            "--reports", "1024", "--total-reports", "2048", "--north-star-reports", "16384", "--cpu-baseline", "0"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -51,7 +51,7 @@ def test_bench_two_ranks_through_the_library_comm_on_one_gpu():
     assert os.path.exists(fake), "run __graft_entry__.build() first"
     env = dict(os.environ, MASTIC_BENCH_DEVICE="0", MASTIC_RCCL_LIB=fake)
     env.pop("MASTIC_BENCH_BACKEND", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "1", "--warmup", "1",
            "--reports", "1024", "--total-reports", "2048", "--north-star-reports", "16384", "--cpu-baseline", "0",
            "--standalone", "0"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=400)
@@ -91,8 +91,9 @@ def test_bench_four_ranks_uneven_job_on_one_gpu():
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    d = _run_bench(["--gpus", "4", "--steps", "1", "--warmup", "1", "--reports", "512", "--total-reports", "512",
-                    "--north-star-reports", "16387", "--cpu-baseline", "0", "--memory-budget-gb", "6"])
+    d = _run_bench(["--full", "--gpus", "4", "--steps", "1", "--warmup", "1", "--reports", "512",
+                    "--total-reports", "512", "--north-star-reports", "16387", "--cpu-baseline", "0",
+                    "--memory-budget-gb", "6"])
     assert d["n_gpus"] == 4 and d["value"] > 0
     ns = d["north_star"]
     assert ns["n_gpus"] == 4 and ns["job_reports"] == 16387
@@ -111,8 +112,8 @@ def test_bench_four_ranks_one_rank_without_reports():
         pytest.skip("no GPU")
     # (--standalone 0: this case is about the empty rank; four ranks sharing one GPU take ~100 s
     # per sweep of 32 merged levels already)
-    d = _run_bench(["--gpus", "4", "--config", "c2sweep", "--split", "1", "--reports", "3", "--steps", "1",
-                    "--warmup", "0", "--cpu-baseline", "0", "--memory-budget-gb", "2", "--standalone", "0"])
+    d = _run_bench(["--full", "--gpus", "4", "--config", "c2sweep", "--split", "1", "--reports", "3", "--steps",
+                    "1", "--warmup", "0", "--cpu-baseline", "0", "--memory-budget-gb", "2", "--standalone", "0"])
     c = d["config"]
     assert d["n_gpus"] == 4 and c["job_reports"] == 3 and c["reports_this_rank"] == 0
     assert c["heavy_hitters_equal_plaintext"] is True
@@ -133,8 +134,8 @@ def test_bench_under_torchrun_uses_the_library_communicator():
     port = s.getsockname()[1]
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
-           "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1",
-           "--warmup", "1", "--reports", "1024", "--total-reports", "2048", "--north-star-reports", "16384",
+           "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps",
+           "1", "--warmup", "1", "--reports", "1024", "--total-reports", "2048", "--north-star-reports", "16384",
            "--cpu-baseline", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -1,5 +1,5 @@
 """Strong-scaling split of the north_star job (bench.py --split, the
-north_star leg of the default bench) on CPU: the job's reports are divided
+north_star leg of bench.py --full) on CPU: the job's reports are divided
 over the ranks, every rank sees the same job-wide per-level aggregates (merged
 over gloo here, RCCL + GPU fold on the box), and all ranks return the heavy
 hitters of the whole job, equal to the single-rank sweep and to the plaintext.
