@@ -40,7 +40,11 @@ MH_D u32x2 chi1(u32x2 a, u32x2 b, u32x2 c) {
 // takes both terms in one 3-input XOR per half (10 fewer XORs per round); it
 // keeps C live through rho, so the 96-VGPR plain level kernel (whose proof
 // waves run this permutation) uses the unfused form: there it doubled the
-// spills and cost C2 1.6 % (profiles/r04_v17_ab_theta_fusion.txt).
+// spills and cost C2 1.6 % (profiles/r04_v17_ab_theta_fusion.txt).  The
+// 104-VGPR level kernel beside the 2-lane sponges (k_eval_aes_wide) runs the
+// fused form.  (Forming each rotl(C[x+1], 1) just before its column, pinned
+// with scheduling barriers, changed no register count there: what spilled was
+// held ACROSS the permutation, not inside it.)
 template <int U = 12, bool FUSE_D = true>
 MH_D void keccak_p12(KState& s) {
     static constexpr uint32_t RCL[12] = {0x8000808bu, 0x0000008bu, 0x00008089u, 0x00008003u,
@@ -100,8 +104,13 @@ struct KHalf {
     uint32_t a[25];
 };
 
+// SWZ: the same exchange as ds_swizzle_b32 (quad-perm mode, [1,0,3,2]): the
+// LDS crossbar instead of a half-rate VALU move; no LDS memory is touched, the
+// result is counted in lgkmcnt.  tools/swizzle_mb.hip measures both.
+template <bool SWZ = false>
 MH_D uint32_t pair_swap(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false);
+    if constexpr (SWZ) return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x80B1);
+    else return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false);
 }
 
 MH_D uint32_t pair_rotl(uint32_t v, int r) {  // r compile-time, r != 32
@@ -110,7 +119,7 @@ MH_D uint32_t pair_rotl(uint32_t v, int r) {  // r compile-time, r != 32
     return r < 32 ? __builtin_amdgcn_alignbit(v, p, 32 - r) : __builtin_amdgcn_alignbit(p, v, 64 - r);
 }
 
-template <int U = 12>
+template <int U = 12, bool SWZ = false>
 MH_D void keccak_p12_pair(KHalf& s, bool hi) {
     static constexpr uint32_t RCL[12] = {0x8000808bu, 0x0000008bu, 0x00008089u, 0x00008003u,
                                          0x00008002u, 0x00000080u, 0x0000800au, 0x8000000au,
@@ -124,14 +133,42 @@ MH_D void keccak_p12_pair(KHalf& s, bool hi) {
         uint32_t C[5], D[5];
 #pragma unroll
         for (int x = 0; x < 5; x++) C[x] = xor3_u32(xor3_u32(A[x], A[x + 5], A[x + 10]), A[x + 15], A[x + 20]);
-#pragma unroll
-        for (int x = 0; x < 5; x++) D[x] = pair_rotl(C[(x + 1) % 5], 1);  // (C[x-1] folded in below)
         uint32_t B[25];
+        if constexpr (SWZ) {
+            // every exchange of a stage is issued before the first is consumed
+            // (the waits the compiler inserts are then counted lgkmcnt waits):
+            // the 5 parities, then the 24 rotated words in two stages of 12
+            // (lgkmcnt is a 4-bit counter: at most 15 outstanding)
+            uint32_t P[5];
 #pragma unroll
-        for (int x = 0; x < 5; x++)
+            for (int x = 0; x < 5; x++) P[x] = pair_swap<true>(C[(x + 1) % 5]);
 #pragma unroll
-            for (int y = 0; y < 5; y++)
-                B[y + 5 * ((2 * x + 3 * y) % 5)] = pair_rotl(xor3_u32(A[x + 5 * y], C[(x + 4) % 5], D[x]), KR(x, y));
+            for (int x = 0; x < 5; x++) D[x] = __builtin_amdgcn_alignbit(C[(x + 1) % 5], P[x], 31);
+            uint32_t T[25], Q[25];
+#pragma unroll
+            for (int i = 0; i < 25; i++) T[i] = xor3_u32(A[i], C[(i % 5 + 4) % 5], D[i % 5]);
+            B[0] = T[0];
+#pragma unroll
+            for (int st = 0; st < 2; st++) {
+#pragma unroll
+                for (int i = 1 + 12 * st; i < 13 + 12 * st; i++) Q[i] = pair_swap<true>(T[i]);
+#pragma unroll
+                for (int i = 1 + 12 * st; i < 13 + 12 * st; i++) {
+                    const int x = i % 5, y = i / 5, r = KR(x, y);
+                    B[y + 5 * ((2 * x + 3 * y) % 5)] = r < 32 ? __builtin_amdgcn_alignbit(T[i], Q[i], 32 - r)
+                                                              : __builtin_amdgcn_alignbit(Q[i], T[i], 64 - r);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int x = 0; x < 5; x++) D[x] = pair_rotl(C[(x + 1) % 5], 1);  // (C[x-1] folded in below)
+#pragma unroll
+            for (int x = 0; x < 5; x++)
+#pragma unroll
+                for (int y = 0; y < 5; y++)
+                    B[y + 5 * ((2 * x + 3 * y) % 5)] =
+                        pair_rotl(xor3_u32(A[x + 5 * y], C[(x + 4) % 5], D[x]), KR(x, y));
+        }
 #pragma unroll
         for (int y = 0; y < 5; y++)
 #pragma unroll

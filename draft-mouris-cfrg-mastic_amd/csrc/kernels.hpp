@@ -729,8 +729,10 @@ MH_D void parent_payload(const AesPerm& TL, const RkLds& rkc, const uint32_t cv[
 #endif
 #define EVAL_PROOF_WAVES 8  // default split (mastic_ctx::proof_waves); measured best of 2..12
 // VGPR cap of the level kernel: 4 waves x 96 per SIMD leave 128 of the 512
-// for one binder-sponge wave (k_absorb_pair), so the two kernels can share a
-// CU instead of taking turns.
+// for one binder-sponge wave, so the two kernels can share a CU instead of
+// taking turns.  The one-lane sponge kernel (k_absorb: 122 VGPRs, allocated
+// 128) needs all of that; the 2-lane one (k_absorb_pair: 93, allocated 96)
+// leaves 32 more, which k_eval_aes_wide below takes.
 // (expressed as a minimum occupancy: 5 waves/SIMD <=> at most 96 VGPRs)
 #ifndef EVAL_MIN_WAVES
 #define EVAL_MIN_WAVES 5
@@ -743,6 +745,14 @@ MH_D void parent_payload(const AesPerm& TL, const RkLds& rkc, const uint32_t cv[
 #define EVAL_FC_MIN_WAVES 4
 #endif
 #define EVAL_VGPR_ATTR __attribute__((amdgpu_waves_per_eu(FC ? EVAL_FC_MIN_WAVES : EVAL_MIN_WAVES)))
+// The plain variants beside 2-lane sponges (WIDE, k_eval_aes_wide): 104 VGPRs,
+// 4 x 104 + 96 = 512.  No occupancy gives 104, so the cap is amdgpu_num_vgpr,
+// which takes a literal (hence a kernel of its own, not a template argument)
+// and which on gfx90a and later, with their unified VGPR / AGPR file, counts
+// HALF of the budget: the compiler doubles it, drops a value above the
+// occupancy's own limit (num_vgpr(104) -> 208 > 128: ignored, 117 allocated)
+// and, since the kernel uses no AGPRs, hands all of it to the VGPRs.  52 -> 104.
+#define EVAL_WIDE_ATTR __attribute__((amdgpu_waves_per_eu(4), amdgpu_num_vgpr(52)))
 // workgroup sync words after the key schedules: [0] parent-run counter, [1]
 // node-proof counter (frontier-cache hits), [8, 40) "child seeds stored" bitmap
 // of the workgroup's parents (<= 16 waves x 64 parents per wave)
@@ -761,9 +771,11 @@ MH_D void parent_payload(const AesPerm& TL, const RkLds& rkc, const uint32_t cv[
 // SPLIT: a small level's parents split into block-range items (AesArgs::split;
 // never with FC); a separate instantiation so the other levels' kernels carry
 // none of its bookkeeping (in the plain kernel it quadrupled the SGPR spills).
-template <class F, bool GEN, bool FC, bool SPLIT = false>
-__global__ __launch_bounds__(64 * EVAL_WAVES) EVAL_VGPR_ATTR
-void k_eval_aes(McParams p, Planes pl, AesArgs a) {
+// WIDE: the 104-VGPR budget above; the proof waves run the fused-theta
+// permutation (never with FC).  One body, two kernels (k_eval_aes and
+// k_eval_aes_wide below) that differ in their register attributes only.
+template <class F, bool GEN, bool FC, bool SPLIT, bool WIDE>
+MH_D void eval_aes_body(const McParams& p, const Planes& pl, const AesArgs& a) {
     typedef typename F::E E;
     // dynamic LDS (EVAL_LDS_BYTES): with a static size the compiler derives
     // the occupancy from it and ignores the VGPR cap of EVAL_VGPR_ATTR
@@ -829,15 +841,33 @@ void k_eval_aes(McParams p, Planes pl, AesArgs a) {
         uint32_t* ohg = a.pv_onehot + (size_t)blockIdx.x * a.oh_gstride;  // tile group of these 64 reports
         const uint32_t lt = (uint32_t)lane * 4u;
         uint32_t pcw[8];
+        if constexpr (!WIDE) {
 #pragma unroll
-        for (int j = 0; j < 8; j++) pcw[j] = pld(pl.cw_proof + ((size_t)pl_ * 8 + j) * S, lb);
+            for (int j = 0; j < 8; j++) pcw[j] = pld(pl.cw_proof + ((size_t)pl_ * 8 + j) * S, lb);
+        }
         for (int node = nbeg; node < nend; node++) {
             uint32_t sd[4];
 #pragma unroll
             for (int i = 0; i < 4; i++) sd[i] = pld(a.cs_in + ((size_t)node * 5 + i) * S_in, lb);
-            const uint32_t t = pld(a.cs_in + ((size_t)node * 5 + 4) * S_in, lb);
-            node_proof_one<FC>(a.np, a.np_f, p.bits, pl_, a.pv_path_bytes, sd, a.pv_child_path + node * 8, t, pcw,
-                           [&](int j, uint32_t w) { pst(ohg + ((size_t)node * 8 + j) * a.bin_rstride, lt, w); });
+            if constexpr (WIDE) {
+                // fused theta keeps the parities live through rho: the control
+                // bit and the proof correction word (the same 8 cached rows for
+                // every node) are loaded after the permutation instead of being
+                // held in 9 registers across it, which spilled them
+                uint32_t w8[8];
+                node_proof_one<true>(a.np, a.np_f, p.bits, pl_, a.pv_path_bytes, sd, a.pv_child_path + node * 8, 0u, pcw,
+                                     [&](int j, uint32_t w) { w8[j] = w; });
+                const uint32_t t = pld(a.cs_in + ((size_t)node * 5 + 4) * S_in, lb);
+#pragma unroll
+                for (int j = 0; j < 8; j++) pcw[j] = pld(pl.cw_proof + ((size_t)pl_ * 8 + j) * S, lb);
+#pragma unroll
+                for (int j = 0; j < 8; j++)
+                    pst(ohg + ((size_t)node * 8 + j) * a.bin_rstride, lt, w8[j] ^ (t ? pcw[j] : 0u));
+            } else {
+                const uint32_t t = pld(a.cs_in + ((size_t)node * 5 + 4) * S_in, lb);
+                node_proof_one<FC>(a.np, a.np_f, p.bits, pl_, a.pv_path_bytes, sd, a.pv_child_path + node * 8, t, pcw,
+                                   [&](int j, uint32_t w) { pst(ohg + ((size_t)node * 8 + j) * a.bin_rstride, lt, w); });
+            }
         }
         if (a.proof_prio) __builtin_amdgcn_s_setprio(0);
         // then help with this workgroup's parents (below)
@@ -1244,6 +1274,17 @@ aes_done:
     }
 }
 
+template <class F, bool GEN, bool FC, bool SPLIT = false>
+__global__ __launch_bounds__(64 * EVAL_WAVES) EVAL_VGPR_ATTR
+void k_eval_aes(McParams p, Planes pl, AesArgs a) {
+    eval_aes_body<F, GEN, FC, SPLIT, false>(p, pl, a);
+}
+template <class F, bool GEN, bool SPLIT = false>
+__global__ __launch_bounds__(64 * EVAL_WAVES) EVAL_WIDE_ATTR
+void k_eval_aes_wide(McParams p, Planes pl, AesArgs a) {
+    eval_aes_body<F, GEN, false, SPLIT, true>(p, pl, a);
+}
+
 // ------------------------------------------------------------- node proofs
 // TurboSHAKE128(seed, dst(ctx, NODE_PROOF), le16(BITS) || le16(l) || path)
 // (vidpf.py:366-380), XORed with the proof CW when the node's control bit is
@@ -1413,6 +1454,11 @@ __global__ __launch_bounds__(256) void k_absorb(Planes pl, AbsorbArgs a) {
 #ifndef ABSORB_MIN_WAVES
 #define ABSORB_MIN_WAVES 5
 #endif
+// partner exchanges through the LDS crossbar (keccak.hpp pair_swap<true>) instead
+// of DPP moves: measured, not adopted; 1 builds the A/B variant
+#ifndef MASTIC_PAIR_SWZ
+#define MASTIC_PAIR_SWZ 0
+#endif
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ABSORB_MIN_WAVES)))
 void k_absorb_pair(Planes pl, AbsorbArgs a) {
     absorb_setprio(a.prio);
@@ -1478,6 +1524,7 @@ void k_absorb_pair(Planes pl, AbsorbArgs a) {
     // before the XOR would make its wait drain them too and expose the whole
     // memory latency once per block).
     uint32_t cur[NL];
+    const uint32_t hmask = 0u - (uint32_t)h;  // all ones on the odd lane
     if (a.dbg == 1 || a.dbg == 4) {
 #pragma unroll
         for (int k = 0; k < NL; k++) cur[k] = lt + k;
@@ -1490,17 +1537,17 @@ void k_absorb_pair(Planes pl, AbsorbArgs a) {
 #pragma unroll
         for (int i = 0; i < 21; i++) {
             // stream word 2i + h + 1: the partner's word i (h = 0) or i + 1 (h = 1)
+            // each lane sends the one word its partner needs (h ? cur[i] : cur[i + 1],
+            // as a bitwise select: a C++ select of two array elements became a per-lane
+            // index into a scratch copy of cur[]): one swap per word
             uint32_t nxt = 0u;
-            if (sh) {
-                const uint32_t x0 = pair_swap(cur[i]), x1 = pair_swap(cur[i + 1]);
-                nxt = h ? x1 : x0;
-            }
+            if (sh) nxt = pair_swap<MASTIC_PAIR_SWZ != 0>((uint32_t)__builtin_amdgcn_bitop3_b32(hmask, cur[i], cur[i + 1], 0xCA));
             s.a[i] ^= __builtin_amdgcn_alignbit(nxt, cur[i], amt);
         }
         if (!full) break;
         asm volatile("" ::: "memory");
         if (more && a.dbg != 1 && a.dbg != 4) load_block(b + 1, cur);
-        if (a.dbg == 0 || a.dbg == 1) keccak_p12_pair(s, h != 0);
+        if (a.dbg == 0 || a.dbg == 1) keccak_p12_pair<12, MASTIC_PAIR_SWZ != 0>(s, h != 0);
         else if (a.dbg == 4) __builtin_amdgcn_s_sleep(72);  // resident, ~4.6k cycles per block, no VALU
         if (!more) break;
     }

@@ -261,6 +261,7 @@ struct mastic_ctx {
     bool hit_absorb_main = true;  // a single-chunk hit's sponges on the main stream (MASTIC_HIT_ABSORB_MAIN=0: sponge stream)
     bool fc_all = false;        // A/B only: the frontier-cache kernel variant at every level (MASTIC_FC_ALL=1)
     bool small_split = true;    // small levels' parents split into block-range items (MASTIC_SMALL_SPLIT=0: off)
+    bool eval_wide = true;      // 104-VGPR level kernel beside the 2-lane sponges (MASTIC_EVAL_WIDE=0: the 96-VGPR one)
     int fuse_proofs = 1;        // last level's node proofs in the level kernel, overlapped with its AES: 1 on
                                 // cache hits, 2 also on cache-on misses, 0 never (MASTIC_FUSE_PROOFS; else
                                 // k_node_proof); 3 (A/B): on hits, after a workgroup barrier
@@ -914,6 +915,7 @@ static int run_chunk(mastic_ctx* c, mastic_reports* rep, const Tree* t, const Wo
     // Sponges which0 .. which0 + nwh - 1 (0 one-hot, 1 payload) of level lv on
     // stream `as` after `ready`; *done marks their end.
     const bool pair = c->absorb_mode == 2 || (c->absorb_mode == 0 && (size_t)n < c->absorb_single_min);
+    const bool wide = pair && c->eval_wide;  // the level kernel may take 104 VGPRs (k_eval_aes_wide)
     auto launch_sponges = [&](int lv, int which0, int nwh, hipEvent_t ready, hipEvent_t e4, hipEvent_t e5,
                               hipStream_t as, hipEvent_t* done) -> int {
         AbsorbArgs ab;
@@ -1101,6 +1103,20 @@ static int run_chunk(mastic_ctx* c, mastic_reports* rep, const Tree* t, const Wo
         // a few per cent)
         if ((lc && (hit || l == t->L || c->fc_all)) || fuse)
             hipLaunchKernelGGL((k_eval_aes<F, true, true>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES, c->stream,
+                               p, pl, a);
+        // beside the 2-lane sponges (96 VGPRs) the plain variants take 104
+        // (k_eval_aes_wide); beside k_absorb (128) they keep 96
+        else if (wide && a.split > 1 && l == 0)
+            hipLaunchKernelGGL((k_eval_aes_wide<F, true, true>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES,
+                               c->stream, p, pl, a);
+        else if (wide && a.split > 1)
+            hipLaunchKernelGGL((k_eval_aes_wide<F, false, true>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES,
+                               c->stream, p, pl, a);
+        else if (wide && (l == 0 || l == t->L))
+            hipLaunchKernelGGL((k_eval_aes_wide<F, true>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES, c->stream,
+                               p, pl, a);
+        else if (wide)
+            hipLaunchKernelGGL((k_eval_aes_wide<F, false>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES, c->stream,
                                p, pl, a);
         else if (a.split > 1 && l == 0)
             hipLaunchKernelGGL((k_eval_aes<F, true, false, true>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES,
@@ -2667,6 +2683,8 @@ extern "C" int mastic_ctx_create(const mastic_params* up, mastic_ctx** out) {
         if (ham) c->hit_absorb_main = ham[0] != '0';
         const char* ssp = getenv("MASTIC_SMALL_SPLIT");
         if (ssp) c->small_split = ssp[0] != '0';
+        const char* evw = getenv("MASTIC_EVAL_WIDE");
+        if (evw) c->eval_wide = evw[0] != '0';
         const char* tnw = getenv("MASTIC_DBG_TIMING_NOWAIT");  // the round-5 last_timing bug, for its test's A/B
         if (tnw) c->timing_nowait = tnw[0] == '1';
         const char* ssr = getenv("MASTIC_SERIAL_SPONGES");
@@ -2694,6 +2712,22 @@ extern "C" int mastic_ctx_create(const mastic_params* up, mastic_ctx** out) {
         hipFuncSetAttribute((const void*)k_eval_aes<F128, true, false, true>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, EVAL_LDS_BYTES) != hipSuccess ||
         hipFuncSetAttribute((const void*)k_eval_aes<F128, false, false, true>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, EVAL_LDS_BYTES) != hipSuccess ||
+        hipFuncSetAttribute((const void*)k_eval_aes_wide<F64, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            EVAL_LDS_BYTES) != hipSuccess ||
+        hipFuncSetAttribute((const void*)k_eval_aes_wide<F128, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            EVAL_LDS_BYTES) != hipSuccess ||
+        hipFuncSetAttribute((const void*)k_eval_aes_wide<F64, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            EVAL_LDS_BYTES) != hipSuccess ||
+        hipFuncSetAttribute((const void*)k_eval_aes_wide<F128, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            EVAL_LDS_BYTES) != hipSuccess ||
+        hipFuncSetAttribute((const void*)k_eval_aes_wide<F64, true, true>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, EVAL_LDS_BYTES) != hipSuccess ||
+        hipFuncSetAttribute((const void*)k_eval_aes_wide<F64, false, true>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, EVAL_LDS_BYTES) != hipSuccess ||
+        hipFuncSetAttribute((const void*)k_eval_aes_wide<F128, true, true>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, EVAL_LDS_BYTES) != hipSuccess ||
+        hipFuncSetAttribute((const void*)k_eval_aes_wide<F128, false, true>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, EVAL_LDS_BYTES) != hipSuccess ||
         hipFuncSetAttribute((const void*)k_absorb_pair, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
             hipSuccess ||
