@@ -599,6 +599,11 @@ struct AesArgs {
     int pv_path_bytes;              // ceil(level / 8)
     const uint32_t* pv_child_path;  // [pv_nodes][8]
     uint32_t* pv_onehot;            // [pv_nodes * 8] proofs of level - 1 (tiled, see AbsorbArgs)
+    // The job is "the proofs of pv_nodes nodes of level pv_level, seeds at
+    // pv_cs" (the work buffer's plane stride): level - 1's nodes in cs_in by
+    // default; a segmented last level (mastic_set_last_level_segments) hands
+    // range q >= 1 the nodes range q - 1 stored in cs_out, pv_level = level.
+    const uint32_t* pv_cs;          // [pv_nodes][5] seeds and control bits of those nodes
     int oh_gstride;                 // words per report group of the proof buffers
     int bin_rstride;                // words between consecutive words of a report in them
     int pay_gstride;                // ... of the payload-difference buffers
@@ -827,7 +832,7 @@ MH_D void eval_aes_body(const McParams& p, const Planes& pl, const AesArgs& a) {
     if (threadIdx.x < EVAL_SYNC_WORDS) next_parent[threadIdx.x] = (SPLIT && threadIdx.x >= 8) ? ~0u : 0u;
     __syncthreads();
     const int aes_waves = a.aes_waves;
-    // Proof waves: node proofs of level - 1 (children seeds from cs_in), then
+    // Proof waves: node proofs of level - 1 (children seeds from pv_cs), then
     // they help with the parents; with no proofs to do (level 0, a frontier-
     // cache hit) they walk parents from the start.  No wave returns early: a
     // cache hit's fused proofs below take nodes from every wave (and the A/B
@@ -848,7 +853,7 @@ MH_D void eval_aes_body(const McParams& p, const Planes& pl, const AesArgs& a) {
         for (int node = nbeg; node < nend; node++) {
             uint32_t sd[4];
 #pragma unroll
-            for (int i = 0; i < 4; i++) sd[i] = pld(a.cs_in + ((size_t)node * 5 + i) * S_in, lb);
+            for (int i = 0; i < 4; i++) sd[i] = pld(a.pv_cs + ((size_t)node * 5 + i) * S, lb);
             if constexpr (WIDE) {
                 // fused theta keeps the parities live through rho: the control
                 // bit and the proof correction word (the same 8 cached rows for
@@ -857,14 +862,14 @@ MH_D void eval_aes_body(const McParams& p, const Planes& pl, const AesArgs& a) {
                 uint32_t w8[8];
                 node_proof_one<true>(a.np, a.np_f, p.bits, pl_, a.pv_path_bytes, sd, a.pv_child_path + node * 8, 0u, pcw,
                                      [&](int j, uint32_t w) { w8[j] = w; });
-                const uint32_t t = pld(a.cs_in + ((size_t)node * 5 + 4) * S_in, lb);
+                const uint32_t t = pld(a.pv_cs + ((size_t)node * 5 + 4) * S, lb);
 #pragma unroll
                 for (int j = 0; j < 8; j++) pcw[j] = pld(pl.cw_proof + ((size_t)pl_ * 8 + j) * S, lb);
 #pragma unroll
                 for (int j = 0; j < 8; j++)
                     pst(ohg + ((size_t)node * 8 + j) * a.bin_rstride, lt, w8[j] ^ (t ? pcw[j] : 0u));
             } else {
-                const uint32_t t = pld(a.cs_in + ((size_t)node * 5 + 4) * S_in, lb);
+                const uint32_t t = pld(a.pv_cs + ((size_t)node * 5 + 4) * S, lb);
                 node_proof_one<FC>(a.np, a.np_f, p.bits, pl_, a.pv_path_bytes, sd, a.pv_child_path + node * 8, t, pcw,
                                    [&](int j, uint32_t w) { pst(ohg + ((size_t)node * 8 + j) * a.bin_rstride, lt, w); });
             }

@@ -243,6 +243,11 @@ struct mastic_ctx {
     int wall_khz = 100000;      // wall_clock64() rate (hipDeviceAttributeWallClockRate)
     bool timing_nowait = false; // A/B of the last_timing fix only (MASTIC_DBG_TIMING_NOWAIT, knob builds)
     bool serial_sponges = false;  // measurement: sponge launches run alone (mastic_set_serial_sponges)
+    // parent ranges of the last level of a cache-less single-stream miss (run_chunk):
+    // 0 = auto, k >= 1 forced (mastic_set_last_level_segments; MASTIC_LAST_LEVEL_SEGMENTS)
+    int last_level_segments = 0;
+    bool seg_early_payload = true;  // ... pay(L-1) on the third stream right after eval(L-1) (MASTIC_SEG_EARLY=0: with oh(L-1))
+    bool seg_balance = true;        // ... ranges of equal proofs per parent (MASTIC_SEG_BALANCE=0: equal parents)
     bool inject_alloc_failure() {
         if (fail_allocs <= 0) return false;
         fail_allocs--;
@@ -774,6 +779,70 @@ static int hit_proof_waves(const McParams& p, const mastic_ctx* c) {
     return std::max(1, std::min(12, (int)std::lround(EVAL_WAVES * K / (K + A))));
 }
 
+// Parent ranges [beg[q], beg[q + 1]) of a last level cut into k segments
+// (run_chunk).  A launch's proof waves get 2 n_parents[L-1] proofs in range 0
+// and the previous range's 2 per parent after that.  The ranges shrink
+// geometrically so that every launch has the same proofs per parent
+// (s_0 = n_parents[L-1] y, s_q = s_{q-1} y, summing to n_parents[L]): the fixed
+// split of a workgroup into AES and proof waves then fits each of them alike,
+// and the last range -- whose proofs k_node_proof computes after the last
+// level kernel -- is the smallest.  (Equal parents, or equal modelled AES +
+// proof work with range 0 the smallest, measured slower:
+// profiles/r08_v1_ab_last_level_segments.txt.)
+static std::vector<int> segment_ranges(const mastic_ctx* c, const Tree* t, int k) {
+    const int npl = t->n_parents[t->L];
+    std::vector<int> beg(k + 1, 0);
+    beg[k] = npl;
+    if (k <= 1) return beg;
+    const double prev = (double)t->n_parents[t->L - 1];
+    std::vector<double> sz(k, (double)npl / k);
+    if (c->seg_balance) {
+        double lo = 0.0, hi = 1.0 + (double)npl / prev;
+        for (int it = 0; it < 60; it++) {
+            const double y = 0.5 * (lo + hi);
+            double sum = 0.0, last = prev;
+            for (int q = 0; q < k; q++) {
+                sz[q] = last * y;
+                last = sz[q];
+                sum += sz[q];
+            }
+            (sum < npl ? lo : hi) = y;
+        }
+    }
+    // cumulative rounding; every range keeps at least one parent (k <= npl)
+    double acc = 0.0;
+    for (int q = 1; q < k; q++) {
+        acc += sz[q - 1];
+        beg[q] = std::max(beg[q - 1] + 1, std::min((int)std::lround(acc), npl - (k - q)));
+    }
+    return beg;
+}
+
+// Segments of the last level of a call that qualifies.  Forced
+// (mastic_set_last_level_segments k >= 1): k, at most one range per parent.
+// Auto: LAST_LEVEL_SEGMENTS_AUTO (the same-box A/B's pick), halved until every
+// range's launch fills the CUs for at least two rounds of workgroups (each
+// launch boundary drains the CUs and refills the tables: a small level gains
+// nothing).
+static constexpr int LAST_LEVEL_SEGMENTS_AUTO = 4;
+static int last_level_segments(const mastic_ctx* c, const Tree* t, int groups, int par_waves) {
+    const int np = t->n_parents[t->L];
+    if (c->last_level_segments >= 1) return std::max(1, std::min(c->last_level_segments, np));
+    int k = std::min(LAST_LEVEL_SEGMENTS_AUTO, np);
+    for (; k > 1; k /= 2) {
+        const std::vector<int> beg = segment_ranges(c, t, k);
+        bool fills = true;
+        for (int q = 0; q < k && fills; q++) {
+            const int cnt = beg[q + 1] - beg[q];
+            const int ppw = choose_eval_ppw(cnt, groups, par_waves, c->n_cus);
+            const long long gy = (cnt + (long long)par_waves * ppw - 1) / ((long long)par_waves * ppw);
+            fills = groups * gy >= 2LL * c->n_cus;
+        }
+        if (fills) break;
+    }
+    return std::max(1, k);
+}
+
 // One chunk of reports [base, base + n) of a prep_init, in work area W.
 // lc: the frontier cache (or null); on a hit the parents are read from
 // cin (the aggregator's node slot); the last level's nodes go to cout (the
@@ -913,21 +982,30 @@ static int run_chunk(mastic_ctx* c, mastic_reports* rep, const Tree* t, const Wo
     auto oh_gs = [&](int) -> int { return oh_gstride; };
     auto pay_gs = [&](int) -> int { return pay_gstride; };
     // Sponges which0 .. which0 + nwh - 1 (0 one-hot, 1 payload) of level lv on
-    // stream `as` after `ready`; *done marks their end.
+    // stream `as` after `ready`; *done marks their end.  With `piece`, only a
+    // contiguous piece of the level's messages (a parent range of a segmented
+    // last level): the proofs of its nodes, the payload differences of its
+    // parents.  The fill positions carry across pieces as across levels.
+    struct Piece {
+        int node0, nodes;      // one-hot sponge: nodes [node0, node0 + nodes) of the level
+        int parent0, parents;  // payload sponge: parents [parent0, parent0 + parents)
+    };
     const bool pair = c->absorb_mode == 2 || (c->absorb_mode == 0 && (size_t)n < c->absorb_single_min);
     const bool wide = pair && c->eval_wide;  // the level kernel may take 104 VGPRs (k_eval_aes_wide)
     auto launch_sponges = [&](int lv, int which0, int nwh, hipEvent_t ready, hipEvent_t e4, hipEvent_t e5,
-                              hipStream_t as, hipEvent_t* done) -> int {
+                              hipStream_t as, hipEvent_t* done, const Piece* piece = nullptr) -> int {
+        const Piece whole{0, 2 * t->n_parents[lv], 0, t->n_parents[lv]};
+        const Piece& pc = piece ? *piece : whole;
         AbsorbArgs ab;
         ab.which0 = which0;
-        ab.seg[0] = oh_buf(lv);
+        ab.seg[0] = oh_buf(lv) + (size_t)pc.node0 * 8 * bin_rstride;
         ab.gstride[0] = oh_gs(lv);
-        ab.nbytes[0] = 2 * t->n_parents[lv] * 32;
+        ab.nbytes[0] = pc.nodes * 32;
         ab.f[0] = f_oh;
-        ab.seg[1] = pay_buf(lv);
+        ab.seg[1] = pay_buf(lv) + (size_t)pc.parent0 * wlw * bin_rstride;
         ab.gstride[1] = pay_gs(lv);
         ab.rstride = bin_rstride;
-        ab.nbytes[1] = lv > 0 ? t->n_parents[lv] * wlw * 4 : 0;
+        ab.nbytes[1] = lv > 0 ? pc.parents * wlw * 4 : 0;
         ab.f[1] = f_pl;
         ab.prio = c->absorb_prio;
         ab.dbg = c->absorb_dbg;
@@ -1013,6 +1091,75 @@ static int run_chunk(mastic_ctx* c, mastic_reports* rep, const Tree* t, const Wo
     // needs them; the cross-stream event round trip cost ~0.08 ms per call),
     // else on the sponge stream after the level's earlier sponges.
     const hipStream_t last_as = (hit && tail == c->stream && c->hit_absorb_main) ? c->stream : ss;
+    // Segmented last level (mastic_set_last_level_segments): a miss with no
+    // frontier cache, not pipelined, beside the 2-lane sponges.  Level L's
+    // parents (BFS order, as are both binder messages) are cut into nseg
+    // contiguous ranges, one level-kernel launch each.  The proof waves of
+    // range 0 take level L-1's node proofs as ever; those of range q >= 1 the
+    // proofs of level L's nodes of range q-1 (from cs_out, which the previous
+    // launch wrote); k_node_proof is left with the last range's nodes.  The
+    // sponges follow piece by piece -- payload piece q after launch q, one-hot
+    // piece q-1 after launch q -- so that what remains after the last level
+    // kernel is one range's proofs and sponge pieces instead of a level and a
+    // half of them.  Every other call keeps one launch per level.
+    const int L_ = t->L;
+    int nseg = 1;
+    if (!lc && !hit && tail == c->stream && ss == c->stream2 && pair && !fuse_last) {
+        const int par_waves = c->par_waves > 0 ? c->par_waves : EVAL_WAVES - c->proof_waves;
+        nseg = last_level_segments(c, t, groups, par_waves);
+    }
+    // Levels L-1 and L then run the split form whatever the field: pay(L-1)
+    // is complete after eval(L-1), so it goes to the third stream at once
+    // (after absorb(L-2), which holds the payload sponge's previous piece)
+    // instead of waiting, paired with oh(L-1), for eval(L)'s first proofs.
+    const bool seg_early = nseg > 1 && c->seg_early_payload && !split && L_ >= 2;
+    const std::vector<int> seg_beg = segment_ranges(c, t, nseg);
+    // timing marks of a sponge piece that has no level-kernel launch of its
+    // own: an event sextuple whose kernel pairs are empty
+    auto piece_marks = [&](hipStream_t as, hipEvent_t* e4, hipEvent_t* e5) -> int {
+        for (int i = 0; i < 4; i++) HIPCHK(c, hipEventRecord(get_event(c, evi++), as));
+        *e4 = get_event(c, evi++);
+        *e5 = get_event(c, evi++);
+        return 0;
+    };
+    // One level-kernel launch (a whole level, or one parent range of a
+    // segmented last level) on the main stream.
+    auto launch_level = [&](const AesArgs& a, dim3 grid, int l, bool fuse) {
+        // the frontier-cache variant only where its features are used: the
+        // last level (convert seeds staged for the cache) and a hit (parent
+        // payloads recomputed, fused proofs); a miss's other levels run the
+        // plain kernel (the variant's uniform branches and extra spills cost
+        // a few per cent)
+        if ((lc && (hit || l == t->L || c->fc_all)) || fuse)
+            hipLaunchKernelGGL((k_eval_aes<F, true, true>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES, c->stream,
+                               p, pl, a);
+        // beside the 2-lane sponges (96 VGPRs) the plain variants take 104
+        // (k_eval_aes_wide); beside k_absorb (128) they keep 96
+        else if (wide && a.split > 1 && l == 0)
+            hipLaunchKernelGGL((k_eval_aes_wide<F, true, true>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES,
+                               c->stream, p, pl, a);
+        else if (wide && a.split > 1)
+            hipLaunchKernelGGL((k_eval_aes_wide<F, false, true>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES,
+                               c->stream, p, pl, a);
+        else if (wide && (l == 0 || l == t->L))
+            hipLaunchKernelGGL((k_eval_aes_wide<F, true>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES, c->stream,
+                               p, pl, a);
+        else if (wide)
+            hipLaunchKernelGGL((k_eval_aes_wide<F, false>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES, c->stream,
+                               p, pl, a);
+        else if (a.split > 1 && l == 0)
+            hipLaunchKernelGGL((k_eval_aes<F, true, false, true>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES,
+                               c->stream, p, pl, a);
+        else if (a.split > 1)
+            hipLaunchKernelGGL((k_eval_aes<F, false, false, true>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES,
+                               c->stream, p, pl, a);
+        else if (l == 0 || l == t->L)
+            hipLaunchKernelGGL((k_eval_aes<F, true, false>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES, c->stream,
+                               p, pl, a);
+        else
+            hipLaunchKernelGGL((k_eval_aes<F, false, false>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES, c->stream,
+                               p, pl, a);
+    };
     for (int l = hit ? t->L : 0; l <= t->L; l++) {
         const int np_ = t->n_parents[l];
         if (!hit && l >= NSLOT) {
@@ -1086,50 +1233,77 @@ static int run_chunk(mastic_ctx* c, mastic_reports* rep, const Tree* t, const Wo
         a.pv_path_bytes = (l + 7) / 8;
         a.pv_child_path = l > 0 ? t->d_path + t->off[l - 1] * 8 : nullptr;
         a.pv_onehot = l > 0 ? oh_buf(l - 1) : nullptr;
+        a.pv_cs = a.cs_in;
         a.oh_gstride = l > 0 ? oh_gs(l - 1) : oh_gstride;
         a.pay_gstride = pay_gs(l);
         a.bin_rstride = bin_rstride;
         a.np = (const PrefixState*)c->pfx.p + PFX_NODE;
         a.np_f = c->pfx_f[PFX_NODE];
+        if (nseg > 1 && l == L_) {
+            // the segmented last level: one launch per parent range
+            for (int q = 0; q < nseg; q++) {
+                const int p0 = seg_beg[q], cnt = seg_beg[q + 1] - p0;
+                AesArgs b = a;
+                b.n_parents = cnt;
+                b.ppw = choose_eval_ppw(cnt, groups, par_waves, c->n_cus);
+                b.parent_node = a.parent_node + p0;
+                b.child_exp = a.child_exp + 2 * (size_t)p0;
+                b.child_pfx = a.child_pfx + 2 * (size_t)p0;
+                b.cur_child_path = a.cur_child_path + 2 * (size_t)p0 * 8;
+                // by child node / parent ordinal of the range: planes of the
+                // work buffer, rows of the (tiled) payload-difference buffer
+                b.cs_out = a.cs_out + 2 * (size_t)p0 * 5 * stride;
+                b.fr_w_in = a.fr_w_in + (size_t)p0 * wlw * stride;
+                b.payload = a.payload + (size_t)p0 * wlw * bin_rstride;
+                if (q > 0) {
+                    // proofs of level L's nodes of range q-1 (the previous launch's cs_out)
+                    const size_t n0 = 2 * (size_t)seg_beg[q - 1];
+                    b.pv_level = l;
+                    b.pv_nodes = 2 * (p0 - seg_beg[q - 1]);
+                    b.pv_path_bytes = (l + 1 + 7) / 8;
+                    b.pv_child_path = t->d_path + (t->off[l] + n0) * 8;
+                    b.pv_onehot = oh_buf(l) + n0 * 8 * bin_rstride;
+                    b.pv_cs = a.cs_out + n0 * 5 * stride;
+                    b.oh_gstride = oh_gs(l);
+                }
+                const int gyq = (cnt + b.par_waves * b.ppw - 1) / (b.par_waves * b.ppw);
+                b.pv_npw = (b.pv_nodes + gyq * pw - 1) / (gyq * pw);
+                hipEvent_t e0 = get_event(c, evi++), e1 = get_event(c, evi++);
+                hipEvent_t e2 = get_event(c, evi++), e3 = get_event(c, evi++);
+                hipEvent_t e4 = get_event(c, evi++), e5 = get_event(c, evi++);
+                HIPCHK(c, hipEventRecord(e0, c->stream));
+                launch_level(b, dim3(groups, gyq), l, false);
+                HIPCHK(c, hipEventRecord(e1, c->stream));
+                HIPCHK(c, hipGetLastError());
+                HIPCHK(c, hipEventRecord(e2, c->stream));
+                HIPCHK(c, hipEventRecord(e3, c->stream));
+                hipEvent_t aes_done = get_sync_event(c, sev++);
+                HIPCHK(c, hipEventRecord(aes_done, c->stream));
+                // the one-hot piece whose proofs this launch made ...
+                if (q > 0) {
+                    const Piece pc{2 * seg_beg[q - 1], 2 * (p0 - seg_beg[q - 1]), 0, 0};
+                    if (launch_sponges(l, 0, 1, aes_done, e4, e5, ss, &abs_done[l], &pc)) return -1;
+                } else if (split || seg_early) {
+                    if (launch_sponges(l - 1, 0, 1, aes_done, e4, e5, ss, &abs_done[l - 1])) return -1;
+                } else {
+                    // both sponges of level L-1; the payload sponge moves to the third stream after it
+                    if (launch_absorb(l - 1, aes_done, e4, e5, ss)) return -1;
+                    HIPCHK(c, hipStreamWaitEvent(c->stream3, abs_done[l - 1], 0));
+                }
+                // ... and this range's payload piece
+                hipEvent_t p4, p5;
+                if (piece_marks(c->stream3, &p4, &p5)) return -1;
+                const Piece pp{0, 0, p0, cnt};
+                if (launch_sponges(l, 1, 1, aes_done, p4, p5, c->stream3, &pl_done[l], &pp)) return -1;
+            }
+            continue;
+        }
         dim3 grid(groups, gy);
         hipEvent_t e0 = get_event(c, evi++), e1 = get_event(c, evi++);
         hipEvent_t e2 = get_event(c, evi++), e3 = get_event(c, evi++);
         hipEvent_t e4 = get_event(c, evi++), e5 = get_event(c, evi++);
         HIPCHK(c, hipEventRecord(e0, c->stream));
-        // the frontier-cache variant only where its features are used: the
-        // last level (convert seeds staged for the cache) and a hit (parent
-        // payloads recomputed, fused proofs); a miss's other levels run the
-        // plain kernel (the variant's uniform branches and extra spills cost
-        // a few per cent)
-        if ((lc && (hit || l == t->L || c->fc_all)) || fuse)
-            hipLaunchKernelGGL((k_eval_aes<F, true, true>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES, c->stream,
-                               p, pl, a);
-        // beside the 2-lane sponges (96 VGPRs) the plain variants take 104
-        // (k_eval_aes_wide); beside k_absorb (128) they keep 96
-        else if (wide && a.split > 1 && l == 0)
-            hipLaunchKernelGGL((k_eval_aes_wide<F, true, true>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES,
-                               c->stream, p, pl, a);
-        else if (wide && a.split > 1)
-            hipLaunchKernelGGL((k_eval_aes_wide<F, false, true>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES,
-                               c->stream, p, pl, a);
-        else if (wide && (l == 0 || l == t->L))
-            hipLaunchKernelGGL((k_eval_aes_wide<F, true>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES, c->stream,
-                               p, pl, a);
-        else if (wide)
-            hipLaunchKernelGGL((k_eval_aes_wide<F, false>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES, c->stream,
-                               p, pl, a);
-        else if (a.split > 1 && l == 0)
-            hipLaunchKernelGGL((k_eval_aes<F, true, false, true>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES,
-                               c->stream, p, pl, a);
-        else if (a.split > 1)
-            hipLaunchKernelGGL((k_eval_aes<F, false, false, true>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES,
-                               c->stream, p, pl, a);
-        else if (l == 0 || l == t->L)
-            hipLaunchKernelGGL((k_eval_aes<F, true, false>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES, c->stream,
-                               p, pl, a);
-        else
-            hipLaunchKernelGGL((k_eval_aes<F, false, false>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES, c->stream,
-                               p, pl, a);
+        launch_level(a, grid, l, fuse);
         HIPCHK(c, hipEventRecord(e1, c->stream));
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipEventRecord(e2, c->stream));
@@ -1142,6 +1316,13 @@ static int run_chunk(mastic_ctx* c, mastic_reports* rep, const Tree* t, const Wo
             if (launch_sponges(l - 1, 0, 1, aes_done, nullptr, nullptr, ss, &abs_done[l - 1])) return -1;
         } else if (l > 0 && !hit) {
             if (launch_absorb(l - 1, aes_done, e4, e5, ss)) return -1;
+            if (seg_early && l == L_ - 1) {
+                // pay(L-1) is complete: on the third stream, after pay(L-2) in the launch above
+                hipEvent_t p4, p5;
+                HIPCHK(c, hipStreamWaitEvent(c->stream3, abs_done[l - 1], 0));
+                if (piece_marks(c->stream3, &p4, &p5)) return -1;
+                if (launch_sponges(l, 1, 1, aes_done, p4, p5, c->stream3, &pl_done[l])) return -1;
+            }
         } else {
             if (c->sponge_delay_us > 0) {
                 // test hook: the sponge stream is still busy when these (empty)
@@ -1173,16 +1354,18 @@ static int run_chunk(mastic_ctx* c, mastic_reports* rep, const Tree* t, const Wo
             return -1;
     } else {
         // the last level's node proofs, then its sponges
+        // (a segmented last level: the last range's; the level kernels made the others)
         const int l = t->L;
-        const int nn = 2 * t->n_parents[l];
+        const int n0 = 2 * seg_beg[nseg - 1];
+        const int nn = 2 * t->n_parents[l] - n0;
         ProofArgs pa;
         pa.level = l;
         pa.n_nodes = nn;
         pa.npw = choose_ppw(nn, groups);
         pa.path_bytes = (l + 1 + 7) / 8;
-        pa.child_path = t->d_path + t->off[l] * 8;
-        pa.cs = plane(wl.cs[l & 1]);
-        pa.onehot = oh_buf(l);
+        pa.child_path = t->d_path + (t->off[l] + (size_t)n0) * 8;
+        pa.cs = plane(wl.cs[l & 1]) + (size_t)n0 * 5 * stride;
+        pa.onehot = oh_buf(l) + (size_t)n0 * 8 * bin_rstride;
         pa.oh_gstride = oh_gs(l);
         pa.bin_rstride = bin_rstride;
         pa.np = (const PrefixState*)c->pfx.p + PFX_NODE;
@@ -1199,8 +1382,10 @@ static int run_chunk(mastic_ctx* c, mastic_reports* rep, const Tree* t, const Wo
         HIPCHK(c, hipGetLastError());
         hipEvent_t np_done = get_sync_event(c, sev++);
         HIPCHK(c, hipEventRecord(np_done, c->stream));
-        if (split ? launch_sponges(l, 0, 1, np_done, e4, e5, last_as, &abs_done[l])
-                  : launch_absorb(l, np_done, e4, e5, last_as))
+        const Piece pc{n0, nn, 0, 0};
+        if (nseg > 1 ? launch_sponges(l, 0, 1, np_done, e4, e5, last_as, &abs_done[l], &pc)
+            : split  ? launch_sponges(l, 0, 1, np_done, e4, e5, last_as, &abs_done[l])
+                     : launch_absorb(l, np_done, e4, e5, last_as))
             return -1;
     }
     hipEvent_t flp_done = nullptr;
@@ -1224,7 +1409,7 @@ static int run_chunk(mastic_ctx* c, mastic_reports* rep, const Tree* t, const Wo
         HIPCHK(c, hipEventRecord(flp_done, c->stream4));
     }
     if (tail != last_as) HIPCHK(c, hipStreamWaitEvent(tail, abs_done[t->L], 0));
-    if (split && pl_done[t->L]) HIPCHK(c, hipStreamWaitEvent(tail, pl_done[t->L], 0));
+    if (pl_done[t->L]) HIPCHK(c, hipStreamWaitEvent(tail, pl_done[t->L], 0));  // split schedule, segmented last level
     FinalArgs fa{agg_id, f_oh, f_pl};
     hipLaunchKernelGGL(k_finalize<F>, dim3((stride + 255) / 256), dim3(256), 0, tail, p, pl, fa, pfx);
     HIPCHK(c, hipGetLastError());
@@ -1461,7 +1646,9 @@ extern "C" int mastic_prep_init(mastic_ctx* c, mastic_reports* rep, const uint8_
     const bool pipe = c->chunk_pipeline && n > chunk && chunk >= 128 && half_cap >= pad + 64;
     if (pipe) chunk = std::min(capped ? chunk : chunk / 2, half_cap - pad) / 64 * 64;
     const size_t half = c->work.bytes / 2 / 4 / 64 * 64;  // words: second half's offset
-    const size_t nsev = 3 * (size_t)t->L + 12;          // sync events one chunk uses
+    // sync events one chunk uses (a segmented last level: three per parent range)
+    const size_t nsev = 3 * (size_t)t->L + 12 +
+                        3 * (size_t)std::min(std::max(c->last_level_segments, LAST_LEVEL_SEGMENTS_AUTO), t->n_parents[t->L]);
     size_t evi = 0;
     hipEvent_t t0 = get_event(c, evi++), t1 = get_event(c, evi++);
     HIPCHK(c, hipEventRecord(t0, c->stream));
@@ -2689,6 +2876,12 @@ extern "C" int mastic_ctx_create(const mastic_params* up, mastic_ctx** out) {
         if (tnw) c->timing_nowait = tnw[0] == '1';
         const char* ssr = getenv("MASTIC_SERIAL_SPONGES");
         if (ssr) c->serial_sponges = ssr[0] == '1';
+        const char* lls = getenv("MASTIC_LAST_LEVEL_SEGMENTS");
+        if (lls) c->last_level_segments = std::max(0, atoi(lls));
+        const char* sge = getenv("MASTIC_SEG_EARLY");
+        if (sge) c->seg_early_payload = sge[0] != '0';
+        const char* sgb = getenv("MASTIC_SEG_BALANCE");
+        if (sgb) c->seg_balance = sgb[0] != '0';
     }
 #endif
     // the level kernel's LDS (table + key schedules) is dynamic, above the
@@ -2802,6 +2995,13 @@ extern "C" int mastic_set_serial_sponges(mastic_ctx* c, int on) {
     if (!c) return MASTIC_EINVAL;
     const int prev = c->serial_sponges ? 1 : 0;
     if (on >= 0) c->serial_sponges = on != 0;
+    return prev;
+}
+
+extern "C" int mastic_set_last_level_segments(mastic_ctx* c, int k) {
+    if (!c || k < 0) return MASTIC_EINVAL;
+    const int prev = c->last_level_segments;
+    c->last_level_segments = k;
     return prev;
 }
 

@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libmastic_hip.so")
 # The library lib() loads: always the shipped in-tree build, unless an A/B tool
 # calls load(path) explicitly (no process variable can swap it).
 LOAD_PATH = LIB_PATH
-ABI_VERSION = 6  # include/mastic_hip.h MASTIC_ABI_VERSION
+ABI_VERSION = 7  # include/mastic_hip.h MASTIC_ABI_VERSION
 
 MASTIC_OK = 0
 ERRORS = {-22: "EINVAL", -12: "ENOMEM", -19: "ENODEV", -5: "EHIP", -110: "ETIMEDOUT"}
@@ -34,7 +34,7 @@ EXPORTS = [
     "mastic_work_bytes", "mastic_last_timing3", "mastic_proof_tree", "mastic_set_frontier_cache",
     "mastic_reports_view", "mastic_decide_results",
     "mastic_aggregate_device_on_stream", "mastic_abi_version", "mastic_set_test_hooks",
-    "mastic_set_test_sponge_delay", "mastic_set_serial_sponges",
+    "mastic_set_test_sponge_delay", "mastic_set_serial_sponges", "mastic_set_last_level_segments",
     "mastic_comm_unique_id", "mastic_comm_init", "mastic_comm_init_timeout", "mastic_comm_info",
     "mastic_comm_destroy",
     "mastic_allgather_fold", "mastic_aggregate_merged", "mastic_merge_host",
@@ -159,6 +159,7 @@ def lib():
                     "mastic_set_test_hooks": (i32, [P, i32, i32]),
                     "mastic_set_test_sponge_delay": (i32, [P, i32]),
                     "mastic_set_serial_sponges": (i32, [P, i32]),
+                    "mastic_set_last_level_segments": (i32, [P, i32]),
                     "mastic_reports_view": (i32, [P, sz, sz, ctypes.POINTER(P)]),
                     "mastic_decide_results": (i32, [P, u8p, sz, P, P]),
                     "mastic_last_timing3": (i32, [P] + [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)] * 3

@@ -422,6 +422,17 @@ class Mastic:
             _check(self._ctx, rc)
         return bool(rc)
 
+    def set_last_level_segments(self, k: int = 0) -> int:
+        """Parent ranges of a prep_init's last level
+        (``mastic_set_last_level_segments``): 0 lets the library choose, k >= 1
+        forces k ranges (at most one per parent).  Only calls with no frontier
+        cache that run as one stream of chunks are segmented.  Results are
+        identical for every k.  Returns the previous setting."""
+        rc = _lib.lib().mastic_set_last_level_segments(self._ctx, int(k))
+        if rc < 0:
+            _check(self._ctx, rc)
+        return rc
+
     def set_frontier_cache(self, on: bool):
         """Keep each prep_init's per-level binder inputs and last frontier in HBM so
         that the next level of a sweep evaluates only its new level (C ABI

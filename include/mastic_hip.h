@@ -56,8 +56,11 @@ extern "C" {
  *    mastic_aggregate_device_on_stream only, so a binary built against an
  *    older header fails to link instead of passing a garbage stream;
  *    mastic_set_serial_sponges (measurement schedule), mastic_set_test_sponge_delay
- *    (test hook). */
-#define MASTIC_ABI_VERSION 6
+ *    (test hook).
+ * 7: mastic_set_last_level_segments (the last level of a prep_init evaluated
+ *    in parent ranges, so its node proofs and binder sponges follow range by
+ *    range instead of after the whole level). */
+#define MASTIC_ABI_VERSION 7
 
 #define MASTIC_OK 0
 #define MASTIC_EINVAL (-22)
@@ -280,6 +283,18 @@ int mastic_set_frontier_cache(mastic_ctx* ctx, int on, int* last_hit);
  * Results are identical either way.  Returns the previous setting (0 / 1) or
  * MASTIC_EINVAL. */
 int mastic_set_serial_sponges(mastic_ctx* ctx, int on);
+/* Parent ranges of a prep_init's last level.  A call with no frontier cache
+ * that runs as one stream of chunks beside the 2-lane sponges evaluates its
+ * last level in k contiguous parent ranges, one level-kernel launch each: the
+ * node proofs of a range are computed by the next launch's proof waves and
+ * both binder sponges absorb the level's messages piece by piece, so only the
+ * last range's proofs and sponge pieces are left after the last level kernel.
+ * k = 0: chosen by the library (1 for a level too small to fill the device
+ * twice per range); k >= 1: forced, at most one range per parent.  Every other
+ * call (frontier cache on, pipelined chunks, one-lane sponges) keeps one
+ * launch per level.  Results are identical for every k.  Returns the previous
+ * setting or MASTIC_EINVAL. */
+int mastic_set_last_level_segments(mastic_ctx* ctx, int k);
 /* Wait for all enqueued work of the ctx. */
 int mastic_synchronize(mastic_ctx* ctx);
 /* The library's MASTIC_ABI_VERSION (a caller built against another header
