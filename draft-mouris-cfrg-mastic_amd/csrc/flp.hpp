@@ -43,6 +43,14 @@ template <class F>
 MH_D void pl_store(uint32_t* plane0, int elt, int stride, int r, typename F::E x) {
     pl_store_rows<F>(plane0, elt, stride, (uint32_t)r * 4u, x);
 }
+// pl_store for an element index that differs between the lanes of a wave
+// (next_vec after a rejection): per-lane addresses instead of the uniform
+// descriptor, which would send every lane's words to the first lane's element.
+template <class F>
+MH_D void pl_store_lane(uint32_t* plane0, int elt, int stride, int r, typename F::E x) {
+#pragma unroll
+    for (int i = 0; i < F::W32; i++) plane0[((size_t)elt * F::W32 + i) * stride + r] = F::word(x, i);
+}
 
 // Field constants needed by the FLP, computed once on the host.
 template <class F>

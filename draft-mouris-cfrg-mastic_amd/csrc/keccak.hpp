@@ -240,7 +240,9 @@ MH_D void sponge_pad(KState& s, int f, uint32_t domain) {
 // order, every W32 of them form a little-endian candidate, candidates >= p
 // are skipped (vdaf_poc.xof.Xof.next_vec).  `put(e, words)` stores element e.
 // Lanes may consume different numbers of candidates (rejection), so the loop
-// runs until every lane of the wave is done.
+// runs until every lane of the wave is done -- and after a rejection the
+// lanes of a wave call put() with different e: it must not treat e as
+// wave-uniform (no pl_store / mh_rsrc, whose descriptor is the first lane's).
 template <int W32, class Valid, class Put>
 MH_D void sponge_squeeze_vec(KState& s, int count, Valid valid, Put put) {
     uint32_t cand[W32];

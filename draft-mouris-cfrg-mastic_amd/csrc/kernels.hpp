@@ -102,6 +102,9 @@ struct Planes {
 };
 
 // ------------------------------------------------------------- unpack
+// per-report verdict of k_validate_wire (mastic_reports::wire_flags)
+#define WIRE_BAD_PUB 1u  // a payload correction word element >= p
+#define WIRE_BAD_LPS 2u  // a leader proof share element >= p
 // nw little-endian words of one report's wire row into plane rows dst[k * step].
 // A == 8: the row, the segment and every report's row start are 8-byte aligned
 // (the common case: BITS a multiple of 32), so a lane reads two words per load
@@ -161,7 +164,7 @@ MH_D void unpack_report(const McParams& p, const Planes& pl, int agg_id, int r, 
 
 __global__ __launch_bounds__(256) void k_unpack(McParams p, Planes pl, int agg_id, const uint8_t* nonces,
                                                 const uint8_t* pub, const uint8_t* ins, int l_lo, int l_hi,
-                                                int big) {
+                                                int big, const uint8_t* wire_flags) {
     // correction words of levels l_lo .. l_hi-1 only: a call at level L never
     // reads deeper ones, and a frontier-cache hit only reads level L's
     const int r = blockIdx.x * 256 + threadIdx.x;
@@ -178,6 +181,48 @@ __global__ __launch_bounds__(256) void k_unpack(McParams p, Planes pl, int agg_i
         unpack_report<8>(p, pl, agg_id, r, ps, is, nc, l_lo, l_hi, big != 0);
     else
         unpack_report<1>(p, pl, agg_id, r, ps, is, nc, l_lo, l_hi);
+    // k_validate_wire's verdict on this aggregator's inputs (the status plane
+    // was cleared just before; k_flp_query may still overwrite it with -2)
+    if (wire_flags[r] & (agg_id == 0 ? WIRE_BAD_PUB | WIRE_BAD_LPS : WIRE_BAD_PUB)) pl.status[r] = -3;
+}
+
+// Field.decode_vec's range check (vdaf_poc field.py: "encoded element out of
+// range") over a report's wire field elements: the payload correction words of
+// every level of the public share (pub != nullptr) and the leader proof share
+// (in0 != nullptr).  Runs once per upload / shard, not per prep_init: the
+// verdict is kept per report (flags[r], WIRE_BAD_* bits; the bits of the
+// segments given are replaced) and k_unpack turns it into status -3.  One wave
+// per report, lanes on consecutive elements.
+template <class F>
+__global__ __launch_bounds__(256) void k_validate_wire(McParams p, int n, const uint8_t* pub, const uint8_t* in0,
+                                                       uint8_t* flags) {
+    const int r = blockIdx.x * 4 + (int)(threadIdx.x >> 6);  // wave-uniform
+    const int lane = threadIdx.x & 63;
+    if (r >= n) return;
+    auto any_bad = [&](const uint8_t* src, int count) {
+        const bool a4 = ((uintptr_t)src & 3) == 0;
+        bool bad = false;
+        for (int e = lane; e < count; e += 64) {
+            uint32_t w[F::W32];
+            const uint8_t* q = src + (size_t)e * F::ENC;
+#pragma unroll
+            for (int i = 0; i < F::W32; i++) w[i] = a4 ? ((const uint32_t*)q)[i] : ld_u32_bytes(q + 4 * i);
+            bad |= !F::valid(F::from_words(w));
+        }
+        return __any(bad) != 0;
+    };
+    uint8_t set = 0, mask = 0;
+    if (pub) {
+        const size_t nctrl = (2 * p.bits + 7) / 8;
+        mask |= WIRE_BAD_PUB;
+        if (any_bad(pub + (size_t)mc_public_share_size(p) * r + nctrl + 16 * (size_t)p.bits, p.bits * p.value_len))
+            set |= WIRE_BAD_PUB;
+    }
+    if (in0) {
+        mask |= WIRE_BAD_LPS;
+        if (any_bad(in0 + (size_t)mc_input_share_size(p, 0) * r + 16, p.proof_len)) set |= WIRE_BAD_LPS;
+    }
+    if (lane == 0) flags[r] = (uint8_t)((flags[r] & ~mask) | set);
 }
 
 // Words [0, nwords) of every report's wire row (row r at src + r * row_bytes,
@@ -1635,7 +1680,7 @@ __global__ __launch_bounds__(256) void k_flp_rand(McParams p, Planes pl, FlpArgs
         return m < 4 ? pl.nonce[m * S + r] : (uint32_t)(a.level & 0xffff);
     });
     sponge_pad(s, f, 0x01);
-    squeeze_elems<F>(s, p.query_rand_len, [&](int e, E x) { pl_store<F>(pl.qr, e, S, r, x); });
+    squeeze_elems<F>(s, p.query_rand_len, [&](int e, E x) { pl_store_lane<F>(pl.qr, e, S, r, x); });
     // proof share: leader from the input share, helper expands its seed
     if (a.agg_id == 0) {
         for (int k = 0; k < p.proof_len * F::W32; k++) pl.proof[(size_t)k * S + r] = pl.lps[(size_t)k * S + r];
@@ -1643,7 +1688,7 @@ __global__ __launch_bounds__(256) void k_flp_rand(McParams p, Planes pl, FlpArgs
         load_prefix(pfx, PFX_PROOF_SHARE, s, f);
         f = sponge_absorb_words(s, f, 32, [&](int m) { return pl.seed[m * S + r]; });
         sponge_pad(s, f, 0x01);
-        squeeze_elems<F>(s, p.proof_len, [&](int e, E x) { pl_store<F>(pl.proof, e, S, r, x); });
+        squeeze_elems<F>(s, p.proof_len, [&](int e, E x) { pl_store_lane<F>(pl.proof, e, S, r, x); });
     }
     if (p.joint_rand_len > 0) {
         // part = TS(seed, dst_alg(JOINT_RAND_PART), nonce || encode(beta_share[1:]))
@@ -1676,7 +1721,7 @@ __global__ __launch_bounds__(256) void k_flp_rand(McParams p, Planes pl, FlpArgs
         load_prefix(pfx, PFX_JR, s, f);
         f = sponge_absorb_words(s, f, 32, [&](int m) { return pl.jr_seed[m * S + r]; });
         sponge_pad(s, f, 0x01);
-        squeeze_elems<F>(s, p.joint_rand_len, [&](int e, E x) { pl_store<F>(pl.jr, e, S, r, x); });
+        squeeze_elems<F>(s, p.joint_rand_len, [&](int e, E x) { pl_store_lane<F>(pl.jr, e, S, r, x); });
     }
 }
 

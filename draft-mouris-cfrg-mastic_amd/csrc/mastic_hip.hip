@@ -173,6 +173,7 @@ struct mastic_reports {
     uint64_t id = next_reports_gen();
     std::shared_ptr<std::atomic<uint64_t>> gen = std::make_shared<std::atomic<uint64_t>>(next_reports_gen());
     DevBuf nonces, pub, in0, in1;
+    DevBuf wire_flags;  // [n] WIRE_BAD_* of k_validate_wire, refreshed by every upload / shard
     void touch() { gen->store(next_reports_gen()); }
     uint64_t generation() const { return gen->load(); }
 };
@@ -919,7 +920,8 @@ static int run_chunk(mastic_ctx* c, mastic_reports* rep, const Tree* t, const Wo
         const bool tiles = row_bytes >= 16384 && (((uintptr_t)pub | (uintptr_t)in_b | ps | is | nctrl) & 7) == 0 &&
                            (max_words + 63) / 64 < 65535;
         hipLaunchKernelGGL(k_unpack, dim3((n + 255) / 256), dim3(256), 0, c->stream, p, pl, agg_id,
-                           rep->nonces.as<uint8_t>() + 16 * base, pub, in_b, l_lo, l_hi, tiles ? 1 : 0);
+                           rep->nonces.as<uint8_t>() + 16 * base, pub, in_b, l_lo, l_hi, tiles ? 1 : 0,
+                           rep->wire_flags.as<uint8_t>() + base);
         if (tiles) {
             const int wlw_ = p.value_len * p.w32, nl = l_hi - l_lo;
             auto rows = [&](const uint8_t* src, size_t row_bytes, int nwords, uint32_t* dst) {
@@ -2606,9 +2608,15 @@ extern "C" int mastic_reports_create(mastic_ctx* c, size_t n, mastic_reports** o
     r->ctx = c;
     r->n = n;
     const McParams& p = c->p;
-    if (!r->nonces.ensure(16 * n) || !r->pub.ensure((size_t)mc_public_share_size(p) * n)) {
+    if (!r->nonces.ensure(16 * n) || !r->pub.ensure((size_t)mc_public_share_size(p) * n) || !r->wire_flags.ensure(n)) {
         delete r;
         return fail(c, MASTIC_ENOMEM, "out of device memory (reports)");
+    }
+    // (null stream, like the blocking copies of upload / shard that follow it there and are done before
+    // the first kernel that touches the flags is queued on the ctx's stream)
+    if (hipMemset(r->wire_flags.p, 0, r->wire_flags.bytes) != hipSuccess) {
+        delete r;
+        return fail(c, MASTIC_EHIP, "reports: clearing the wire flags failed");
     }
     *out = r;
     return 0;
@@ -2629,6 +2637,7 @@ extern "C" int mastic_reports_view(mastic_reports* rep, size_t first, size_t cou
     r->pub.view(rep->pub, ps * first, ps * count);
     r->in0.view(rep->in0, i0 * first, i0 * count);
     r->in1.view(rep->in1, i1 * first, i1 * count);
+    r->wire_flags.view(rep->wire_flags, first, count);
     *out = r;
     return 0;
 }
@@ -2638,6 +2647,24 @@ extern "C" void mastic_reports_destroy(mastic_reports* r) {
     delete r;
 }
 extern "C" size_t mastic_reports_count(const mastic_reports* r) { return r ? r->n : 0; }
+
+// Range check of the wire field elements of the segments just written (pub:
+// the public shares, in0: the leader input shares), queued on the ctx's
+// stream ahead of any prep_init over the batch.
+static int validate_wire(mastic_ctx* c, mastic_reports* r, bool pub, bool in0) {
+    if (r->n == 0 || (!pub && !in0)) return 0;
+    const dim3 grid((unsigned)((r->n + 3) / 4));
+    const uint8_t* dp = pub ? r->pub.as<uint8_t>() : nullptr;
+    const uint8_t* di = in0 ? r->in0.as<uint8_t>() : nullptr;
+    if (c->p.field == 64)
+        hipLaunchKernelGGL(k_validate_wire<F64>, grid, dim3(256), 0, c->stream, c->p, (int)r->n, dp, di,
+                           r->wire_flags.as<uint8_t>());
+    else
+        hipLaunchKernelGGL(k_validate_wire<F128>, grid, dim3(256), 0, c->stream, c->p, (int)r->n, dp, di,
+                           r->wire_flags.as<uint8_t>());
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
 
 extern "C" int mastic_reports_upload(mastic_reports* r, const uint8_t* nonces, const uint8_t* pub,
                                      const uint8_t* in0, const uint8_t* in1) {
@@ -2657,7 +2684,7 @@ extern "C" int mastic_reports_upload(mastic_reports* r, const uint8_t* nonces, c
         if (!r->in1.ensure((size_t)mc_input_share_size(p, 1) * n)) return fail(c, MASTIC_ENOMEM, "out of device memory");
         HIPCHK(c, hipMemcpy(r->in1.p, in1, (size_t)mc_input_share_size(p, 1) * n, hipMemcpyHostToDevice));
     }
-    return 0;
+    return validate_wire(c, r, pub != nullptr, in0 != nullptr);
 }
 
 extern "C" int mastic_reports_download(mastic_reports* r, uint8_t* nonces, uint8_t* pub, uint8_t* in0, uint8_t* in1) {
@@ -2752,6 +2779,7 @@ static int shard_impl(mastic_ctx* c, mastic_reports* rep, const uint8_t* alphas,
                            (const PrefixState*)c->pfx.p, fc, tab.as<E>());
         HIPCHK(c, hipGetLastError());
     }
+    if (int rc = validate_wire(c, rep, true, true)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -242,7 +242,7 @@ __global__ __launch_bounds__(256) void k_shard(McParams p, ShardArgs a, const Pr
         load_prefix(pfx, PFX_JR, s, f);
         f = sponge_absorb_words(s, f, 32, [&](int m) { return a.misc[(20 + m) * S + r]; });
         sponge_pad(s, f, 0x01);
-        squeeze_elems<F>(s, p.joint_rand_len, [&](int e, E x) { pl_store<F>(a.jr, e, S, r, x); });
+        squeeze_elems<F>(s, p.joint_rand_len, [&](int e, E x) { pl_store_lane<F>(a.jr, e, S, r, x); });
     }
     {
         KState s;
@@ -251,7 +251,7 @@ __global__ __launch_bounds__(256) void k_shard(McParams p, ShardArgs a, const Pr
         load_prefix(pfx, PFX_PROVE_RAND, s, f);
         f = sponge_absorb_words(s, f, 32, [&](int m) { return a.misc[(4 + m) * S + r]; });
         sponge_pad(s, f, 0x01);
-        squeeze_elems<F>(s, p.prove_rand_len, [&](int e, E x) { pl_store<F>(a.prand, e, S, r, x); });
+        squeeze_elems<F>(s, p.prove_rand_len, [&](int e, E x) { pl_store_lane<F>(a.prand, e, S, r, x); });
     }
     flp_prove<F>(p, fc, alpha_inv_pows, a.beta + (size_t)F::W32 * S, a.jr, a.prand, a.vals, a.coef, a.proof, S, r);
     {
@@ -261,7 +261,7 @@ __global__ __launch_bounds__(256) void k_shard(McParams p, ShardArgs a, const Pr
         load_prefix(pfx, PFX_PROOF_SHARE, s, f);
         f = sponge_absorb_words(s, f, 32, [&](int m) { return a.misc[(4 + m) * S + r]; });
         sponge_pad(s, f, 0x01);
-        squeeze_elems<F>(s, p.proof_len, [&](int e, E x) { pl_store<F>(a.hps, e, S, r, x); });
+        squeeze_elems<F>(s, p.proof_len, [&](int e, E x) { pl_store_lane<F>(a.hps, e, S, r, x); });
     }
     // ---- input shares (mastic.py:516-529)
     uint8_t* o0 = a.in0 + (size_t)mc_input_share_size(p, 0) * r;

@@ -17,6 +17,10 @@ from . import _lib
 from .field import Field64, Field128
 
 PROOF_SIZE = 32
+# per-report status of prep_init (include/mastic_hip.h MASTIC_STATUS_*)
+STATUS_OK = 0
+STATUS_QUERY_ABORT = -2    # FlpBBCGGI19.query: the test point is a root of unity
+STATUS_NONCANONICAL = -3   # a wire field element (payload correction word, leader proof share) is >= p
 CIRCUIT_IDS = {"Count": 1, "Sum": 2, "SumVec": 3, "Histogram": 4, "MultihotCountVec": 5}
 
 
@@ -187,7 +191,8 @@ class Mastic:
     def prep_init_batch(self, verify_key: bytes, ctx: bytes, agg_id: int, agg_param, nonces: bytes,
                         public_shares: bytes, input_shares: bytes, want_out_shares=True):
         """prep_init for n reports (wire in, wire out).  Returns
-        (prep_shares bytes, jr_seeds bytes, out_shares bytes or None, status int32 array)."""
+        (prep_shares bytes, jr_seeds bytes, out_shares bytes or None, status int32 array);
+        status is 0 or a negative STATUS_* code (such a report is to be rejected)."""
         enc = self.encode_agg_param(agg_param) if not isinstance(agg_param, (bytes, bytearray)) else bytes(agg_param)
         (level, count, wc) = self._agg_param_header(enc)
         n = len(nonces) // 16
@@ -515,6 +520,8 @@ class Mastic:
         pub = self.encode_public_share(public_share)
         ins = self.test_vec_encode_input_share(input_share)
         (ps, js, out, st) = self.prep_init_batch(verify_key, ctx, agg_id, agg_param, nonce, pub, ins)
+        if st[0] == STATUS_NONCANONICAL:
+            raise ValueError("encoded element out of range")
         if st[0] != 0:
             raise ValueError("test point is a root of unity")
         prep_share = self.decode_prep_share(wc, ps)

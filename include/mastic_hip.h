@@ -118,7 +118,10 @@ int mastic_reports_create(mastic_ctx* ctx, size_t n, mastic_reports** out);
 void mastic_reports_destroy(mastic_reports* rep);
 size_t mastic_reports_count(const mastic_reports* rep);
 /* nonces n*16, public_shares n*public_share_size, input_shares{0,1}
- * n*input_share_size[agg]; either input-share pointer may be NULL. */
+ * n*input_share_size[agg]; either input-share pointer may be NULL.  The field
+ * elements of the public shares and of the leader proof shares given are
+ * range-checked here (MASTIC_STATUS_NONCANONICAL of every later prep_init over
+ * the batch or a view of it). */
 int mastic_reports_upload(mastic_reports* rep, const uint8_t* nonces, const uint8_t* public_shares,
                           const uint8_t* input_shares0, const uint8_t* input_shares1);
 int mastic_reports_download(mastic_reports* rep, uint8_t* nonces, uint8_t* public_shares,
@@ -147,7 +150,18 @@ int mastic_prep_init(mastic_ctx* ctx, mastic_reports* rep, const uint8_t* verify
  * may be NULL.  prep_shares n*prep_share_size[weight_check] (wire encoding,
  * mastic.py:543-552); jr_seeds n*32 (zero when not applicable);
  * out_shares n*len(prefixes)*(1+output_len)*field_bytes (truncated output
- * shares = prep_state[0], encode_vec); status n (0 = ok, <0 = query abort). */
+ * shares = prep_state[0], encode_vec); status n: MASTIC_STATUS_* below.  A
+ * report with a nonzero status is never accepted by mastic_decide_results;
+ * its other outputs are unspecified. */
+#define MASTIC_STATUS_OK 0
+#define MASTIC_STATUS_QUERY_ABORT (-2)   /* FlpBBCGGI19.query: the test point is a root of unity */
+#define MASTIC_STATUS_NONCANONICAL (-3)  /* a wire field element of this aggregator's input is >= p: a payload
+                                          * correction word of any level of the public share, or (agg_id 0) an
+                                          * element of the leader proof share.  The reference's decoders raise
+                                          * ValueError("encoded element out of range") for such a report
+                                          * (vdaf_poc field.py decode_vec).  Checked once per
+                                          * mastic_reports_upload / mastic_reports_shard, over the whole share:
+                                          * a bad element below the call's level rejects the report too. */
 int mastic_prep_result(mastic_ctx* ctx, int agg_id, uint8_t* prep_shares, uint8_t* jr_seeds, uint8_t* out_shares,
                        int32_t* status);
 /* Both aggregators' prep_shares_to_prep + prep_next (mastic.py:320-377) for

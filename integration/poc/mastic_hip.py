@@ -162,6 +162,8 @@ class MasticHip:
         with_seed = do_weight_check and m.flp.JOINT_RAND_LEN > 0  # mastic.py:236-248
         out = []
         for i in range(n):
+            if status[i] == -3:  # MASTIC_STATUS_NONCANONICAL: the poc's decoders raise this (field.py decode_vec)
+                raise ValueError("encoded element out of range")
             if status[i] != 0:  # FlpBBCGGI19.query aborted (t^P == 1): the poc raises there
                 raise Exception("FLP query failed for report %d" % i)
             truncated = m.field.decode_vec(out_shares.raw[osz * i:osz * (i + 1)])
