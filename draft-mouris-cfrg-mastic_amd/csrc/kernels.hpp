@@ -777,7 +777,7 @@ MH_D void parent_payload(const AesPerm& TL, const RkLds& rkc, const uint32_t cv[
 #ifndef MASTIC_CTR_GROUPS
 #define MASTIC_CTR_GROUPS 1
 #endif
-#define EVAL_PROOF_WAVES 8  // default split (mastic_ctx::proof_waves); measured best of 2..12
+#define EVAL_PROOF_WAVES 8  // default split (schedule.hpp SchedKnobs::proof_waves); measured best of 2..12
 // VGPR cap of the level kernel: 4 waves x 96 per SIMD leave 128 of the 512
 // for one binder-sponge wave, so the two kernels can share a CU instead of
 // taking turns.  The one-lane sponge kernel (k_absorb: 122 VGPRs, allocated

@@ -27,7 +27,12 @@
 #include "comm_agree.hpp"
 #include "host_tree.hpp"
 #include "kernels.hpp"
+#include "schedule.hpp"
 #include "shard.hpp"
+
+static_assert(SCHED_EVAL_WAVES == EVAL_WAVES && SCHED_EVAL_PROOF_WAVES == EVAL_PROOF_WAVES &&
+                  SCHED_SPONGE_RATE == KECCAK_RATE,
+              "schedule.hpp and the kernels disagree on a shared constant");
 
 namespace {
 
@@ -209,25 +214,14 @@ struct mastic_ctx {
     DevBuf agg_valid, agg_out;  // mastic_aggregate staging
     DevBuf agg_part;            // per-chunk partial sums of a split fold (aggregate_impl)
     DevBuf stage;               // result encoding / decide staging
-    // Lanes per binder sponge.  Two (k_absorb_pair: half the dependent chain
-    // per permutation, ~1.5x the VALU issue slots) while the chains are the
-    // critical path, i.e. a chunk of few reports (C2's 16,384: one sponge wave
-    // for every second SIMD); one (k_absorb: a third fewer VALU slots taken
-    // from the level kernel beside it) once a chunk has enough reports for the
-    // sponges to be throughput-bound (the 1M-report sweep's ~380k-report
-    // chunks).  Same-box A/B (profiles/r05_v6_ab_single_lane_sponges.txt): one
-    // lane is +4.5 % on the 1M sweep, -2 % on C2 and -21 % on C5 at 16,384.
-    // 0 = by chunk size (>= absorb_single_min reports: one lane), 1 = always
-    // one, 2 = always two (MASTIC_ABSORB_SINGLE).
-    int absorb_mode = 0;
-    size_t absorb_single_min = 65536;  // MASTIC_ABSORB_SINGLE_MIN
+    SchedKnobs k;               // the knobs the launch plan reads (schedule.hpp)
+    ChunkPlan plans[2];         // the last prep_init's plans (full chunk, last chunk): their vectors are reused
+    // the running chunk's sponge ends: per planned sponge launch, and the last
+    // piece of the one-hot / payload sponge of each level (run_plan)
+    std::vector<hipEvent_t> sp_done, oh_done, pl_done;
     int absorb_lds = 0;         // bytes of dynamic LDS per absorb workgroup (MASTIC_ABSORB_LDS_KB)
-    int n_cus = 256;                     // compute units of the device
-    int proof_waves = EVAL_PROOF_WAVES;  // proof waves per eval workgroup (MASTIC_PROOF_WAVES)
-    int hit_proof_waves = 0;             // ... of a fused-proof hit launch (0 = by the work split; MASTIC_HIT_PROOF_WAVES)
-    int proof_prio = 0;                  // their s_setprio (MASTIC_PROOF_PRIO)
+    int proof_prio = 0;                  // s_setprio of the level kernel's proof waves (MASTIC_PROOF_PRIO)
     int aes_prio = 0;                    // s_setprio of the AES waves (MASTIC_AES_PRIO)
-    int dbg_skip = 0;                    // timing experiments only (MASTIC_DBG_SKIP; results wrong): 1 no node proofs, 2 no AES, 4 no binder sponges
     int stride_pad = 64;                 // words of padding per plane row (MASTIC_STRIDE_PAD)
     size_t work_arena = (size_t)48 << 30;  // minimum size of a new work buffer (MASTIC_WORK_ARENA_GB)
     // ... with the frontier cache on (level sweeps, whose trees grow from level to level): large
@@ -244,11 +238,6 @@ struct mastic_ctx {
     int wall_khz = 100000;      // wall_clock64() rate (hipDeviceAttributeWallClockRate)
     bool timing_nowait = false; // A/B of the last_timing fix only (MASTIC_DBG_TIMING_NOWAIT, knob builds)
     bool serial_sponges = false;  // measurement: sponge launches run alone (mastic_set_serial_sponges)
-    // parent ranges of the last level of a cache-less single-stream miss (run_chunk):
-    // 0 = auto, k >= 1 forced (mastic_set_last_level_segments; MASTIC_LAST_LEVEL_SEGMENTS)
-    int last_level_segments = 0;
-    bool seg_early_payload = true;  // ... pay(L-1) on the third stream right after eval(L-1) (MASTIC_SEG_EARLY=0: with oh(L-1))
-    bool seg_balance = true;        // ... ranges of equal proofs per parent (MASTIC_SEG_BALANCE=0: equal parents)
     bool inject_alloc_failure() {
         if (fail_allocs <= 0) return false;
         fail_allocs--;
@@ -261,19 +250,8 @@ struct mastic_ctx {
         return hipStreamSynchronize(stream) == hipSuccess && hipStreamSynchronize(stream2) == hipSuccess &&
                hipStreamSynchronize(stream3) == hipSuccess && hipStreamSynchronize(stream4) == hipSuccess;
     }
-    int split_sponges = -1;  // payload sponge a level earlier, on the third stream: -1 Field128 only, 0 never, 1 always (MASTIC_SPLIT_SPONGES)
-    bool fuse_last_miss = false;    // any miss's last level with fused, overlapped node proofs (MASTIC_FUSE_LAST_MISS=1)
-    bool fuse_last_miss_fc = true;  // ... a cache-on miss's (MASTIC_FUSE_LAST_MISS_FC=0: k_node_proof)
-    bool hit_absorb_main = true;  // a single-chunk hit's sponges on the main stream (MASTIC_HIT_ABSORB_MAIN=0: sponge stream)
-    bool fc_all = false;        // A/B only: the frontier-cache kernel variant at every level (MASTIC_FC_ALL=1)
-    bool small_split = true;    // small levels' parents split into block-range items (MASTIC_SMALL_SPLIT=0: off)
-    bool eval_wide = true;      // 104-VGPR level kernel beside the 2-lane sponges (MASTIC_EVAL_WIDE=0: the 96-VGPR one)
-    int fuse_proofs = 1;        // last level's node proofs in the level kernel, overlapped with its AES: 1 on
-                                // cache hits, 2 also on cache-on misses, 0 never (MASTIC_FUSE_PROOFS; else
-                                // k_node_proof); 3 (A/B): on hits, after a workgroup barrier
     size_t chunk_max = 0;        // reports per chunk cap (0 = what fits; MASTIC_CHUNK_REPORTS)
     bool chunk_pipeline = true;  // several chunks: two halves of the work arena (MASTIC_CHUNK_PIPELINE=0: off)
-    int par_waves = 0;           // waves' worth of parents per level-kernel workgroup (0 = by field; MASTIC_PAR_WAVES)
     int pfx_f[PFX_COUNT] = {0};  // fill position of each prefix state (host copy)
     std::vector<uint8_t> pfx_key;  // verify key || ctx of the prefix states in pfx (empty: none)
     std::map<std::vector<uint8_t>, Tree*> trees;
@@ -587,7 +565,6 @@ struct WorkLayout {
         rootsum, beta, eval_proof, proof, qr, jr, jr_part, jr_seed, verifier, status, cs[2], fr_w[2], onehot[3],
         payload[3];
 };
-static constexpr int NSLOT = 3;  // level buffers in flight between eval and absorb
 
 static WorkLayout work_layout(const McParams& p, const Tree* t) {
     WorkLayout w;
@@ -664,86 +641,17 @@ static Planes make_planes(uint32_t* base, const WorkLayout& w, int n, int stride
     return pl;
 }
 
-static hipEvent_t get_sync_event(mastic_ctx* c, size_t i) {
-    while (c->sync_ev.size() <= i) {
+// Event i of a pool that grows on demand.
+static hipEvent_t event_at(std::vector<hipEvent_t>& pool, size_t i, unsigned flags) {
+    while (pool.size() <= i) {
         hipEvent_t e;
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return nullptr;
-        c->sync_ev.push_back(e);
+        if (hipEventCreateWithFlags(&e, flags) != hipSuccess) return nullptr;
+        pool.push_back(e);
     }
-    return c->sync_ev[i];
+    return pool[i];
 }
-
-static hipEvent_t get_event(mastic_ctx* c, size_t i) {
-    while (c->tm[c->tcur].ev.size() <= i) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return nullptr;
-        c->tm[c->tcur].ev.push_back(e);
-    }
-    return c->tm[c->tcur].ev[i];
-}
-
-
-// ---------------------------------------------------------------- prep_init
-// Parents per wave: enough waves to fill 256 CUs several times over.
-static int choose_ppw(int n_parents, int groups) {
-    long long per = (long long)n_parents * groups / 16384;
-    return (int)std::max(1LL, std::min(per, 64LL));
-}
-
-// Parents per AES wave of the level kernel.  A level is one launch and the
-// next level's launch waits for its last workgroup, so the workgroup count
-// should fill whole rounds of the CUs (one workgroup per CU) with nearly full
-// workgroups: pick, among 8..64 parents per wave, the count whose
-// (work / (rounds x CUs)) is highest, preferring more parents per wave (fewer
-// table fills) within 0.5 %.
-static int choose_eval_ppw(int n_parents, int groups, int aes_waves, int n_cus) {
-    if ((long long)n_parents * groups < (long long)aes_waves * 8 * n_cus) return choose_ppw(n_parents, groups * 2);
-    double best_eff = -1.0;
-    int best = 64;
-    for (int ppw = 64; ppw >= 8; ppw--) {
-        const long long gy = (n_parents + (long long)aes_waves * ppw - 1) / ((long long)aes_waves * ppw);
-        const long long rounds = (groups * gy + n_cus - 1) / n_cus;
-        const double work = (double)groups * n_parents / ((double)aes_waves * ppw);
-        const double eff = work / ((double)rounds * n_cus);
-        if (eff > best_eff + 0.005) {
-            best_eff = eff;
-            best = ppw;
-        }
-    }
-    return best;
-}
-
-// Items per parent at a small level (AesArgs::split).  A workgroup's 16
-// waves share its items; a parent's AES is 2 extend blocks plus nblk convert
-// blocks per child (next seed + payload: 2 + 2 nblk in lockstep pairs).  With
-// few parents the launch time is the workgroup's longest serial chain:
-// items per wave x blocks per item.  Pick the split minimising that (each
-// item recomputes the extend pair; item 0 adds the next-seed pair), fewer
-// items on ties.  At 16 or more parents this is 1 (no split).
-// The proof waves first compute level l-1's node proofs (2 np_prev per
-// report, spread over them; ~3 AES blocks of time per Keccak-p, the ratio
-// miss_proof_waves uses) and then claim items from the same LDS counter, so
-// the 16 waves' capacity is reduced by that head start.
-static void choose_split(int n_parents, int np_prev, int proof_waves, int nblk, int* split, int* split_blocks) {
-    int best_k = 1, best_cost = 1 << 30;
-    const int pw = std::max(1, proof_waves);
-    const int proof_blocks = np_prev > 0 ? pw * ((2 * np_prev + pw - 1) / pw) * 3 : 0;
-    for (int k = 1; k <= nblk; k++) {
-        const int nb = (nblk + k - 1) / k;
-        const int kk = (nblk + nb - 1) / nb;  // ranges actually non-empty
-        if (kk != k) continue;
-        const int chain = 2 + 2 * nb;
-        // the items' waves: whole items per wave after the proof waves' head start
-        const int per_wave = (n_parents * k * chain + proof_blocks + EVAL_WAVES * chain - 1) / (EVAL_WAVES * chain);
-        const int cost = per_wave * chain + 2;
-        if (cost < best_cost) {
-            best_cost = cost;
-            best_k = k;
-        }
-    }
-    *split = best_k;
-    *split_blocks = (nblk + best_k - 1) / best_k;
-}
+static hipEvent_t get_sync_event(mastic_ctx* c, size_t i) { return event_at(c->sync_ev, i, hipEventDisableTiming); }
+static hipEvent_t get_event(mastic_ctx* c, size_t i) { return event_at(c->tm[c->tcur].ev, i, hipEventDefault); }
 
 static int copy_planes(mastic_ctx* c, DevBuf& dst, size_t dst_stride, size_t dst_off, const uint32_t* src,
                        size_t src_stride, size_t n, size_t planes, hipStream_t s) {
@@ -753,155 +661,105 @@ static int copy_planes(mastic_ctx* c, DevBuf& dst, size_t dst_stride, size_t dst
     return 0;
 }
 
-// Proof waves of a level kernel whose node proofs are fused and overlapped
-// (a frontier-cache hit, kernels.hpp fuse_ovl): the proofs' share of the work
-// per parent, two Keccak-p (VALU, ~3.2k CU-cycles) against the AES of the
-// extend pair, the convert seeds, both children's payload blocks and the
-// parent-payload recompute, 4 + 3 nblk blocks (LDS: 2 x 133 cycles per block
-// at the kernel's ~50 % LDS efficiency).  C3 (Count): 7 of 16, the c2sweep
-// (Sum 255, 9 payload blocks): 3.
-// ... and of a miss's fused last level: per parent also the extend pair and,
-// with no recompute, 3 + 2 nblk AES blocks; the proof waves also take level
-// L-1's node proofs first (2 np[L-1] of them, spread over level L's parents).
-static int miss_proof_waves(const McParams& p, const mastic_ctx* c, int np_prev, int np_last, bool has_prev) {
-    if (c->hit_proof_waves > 0) return c->hit_proof_waves;
-    const int epb = p.field == 64 ? 2 : 1;
-    const int nblk = (p.value_len + epb - 1) / epb;
-    const double proofs = 2.0 + (has_prev ? 2.0 * np_prev / std::max(1, np_last) : 0.0);
-    const double K = 1585.0 * proofs, A = (4.0 + 2.0 * nblk) * 532.0;
-    return std::max(1, std::min(12, (int)std::lround(EVAL_WAVES * K / (K + A))));
-}
-
-static int hit_proof_waves(const McParams& p, const mastic_ctx* c) {
-    if (c->hit_proof_waves > 0) return c->hit_proof_waves;
-    const int epb = p.field == 64 ? 2 : 1;
-    const int nblk = (p.value_len + epb - 1) / epb;
-    const double K = 3170.0, A = (4.0 + 3.0 * nblk) * 532.0;
-    return std::max(1, std::min(12, (int)std::lround(EVAL_WAVES * K / (K + A))));
-}
-
-// Parent ranges [beg[q], beg[q + 1]) of a last level cut into k segments
-// (run_chunk).  A launch's proof waves get 2 n_parents[L-1] proofs in range 0
-// and the previous range's 2 per parent after that.  The ranges shrink
-// geometrically so that every launch has the same proofs per parent
-// (s_0 = n_parents[L-1] y, s_q = s_{q-1} y, summing to n_parents[L]): the fixed
-// split of a workgroup into AES and proof waves then fits each of them alike,
-// and the last range -- whose proofs k_node_proof computes after the last
-// level kernel -- is the smallest.  (Equal parents, or equal modelled AES +
-// proof work with range 0 the smallest, measured slower:
-// profiles/r08_v1_ab_last_level_segments.txt.)
-static std::vector<int> segment_ranges(const mastic_ctx* c, const Tree* t, int k) {
-    const int npl = t->n_parents[t->L];
-    std::vector<int> beg(k + 1, 0);
-    beg[k] = npl;
-    if (k <= 1) return beg;
-    const double prev = (double)t->n_parents[t->L - 1];
-    std::vector<double> sz(k, (double)npl / k);
-    if (c->seg_balance) {
-        double lo = 0.0, hi = 1.0 + (double)npl / prev;
-        for (int it = 0; it < 60; it++) {
-            const double y = 0.5 * (lo + hi);
-            double sum = 0.0, last = prev;
-            for (int q = 0; q < k; q++) {
-                sz[q] = last * y;
-                last = sz[q];
-                sum += sz[q];
-            }
-            (sum < npl ? lo : hi) = y;
-        }
-    }
-    // cumulative rounding; every range keeps at least one parent (k <= npl)
-    double acc = 0.0;
-    for (int q = 1; q < k; q++) {
-        acc += sz[q - 1];
-        beg[q] = std::max(beg[q - 1] + 1, std::min((int)std::lround(acc), npl - (k - q)));
-    }
-    return beg;
-}
-
-// Segments of the last level of a call that qualifies.  Forced
-// (mastic_set_last_level_segments k >= 1): k, at most one range per parent.
-// Auto: LAST_LEVEL_SEGMENTS_AUTO (the same-box A/B's pick), halved until every
-// range's launch fills the CUs for at least two rounds of workgroups (each
-// launch boundary drains the CUs and refills the tables: a small level gains
-// nothing).
-static constexpr int LAST_LEVEL_SEGMENTS_AUTO = 4;
-static int last_level_segments(const mastic_ctx* c, const Tree* t, int groups, int par_waves) {
-    const int np = t->n_parents[t->L];
-    if (c->last_level_segments >= 1) return std::max(1, std::min(c->last_level_segments, np));
-    int k = std::min(LAST_LEVEL_SEGMENTS_AUTO, np);
-    for (; k > 1; k /= 2) {
-        const std::vector<int> beg = segment_ranges(c, t, k);
-        bool fills = true;
-        for (int q = 0; q < k && fills; q++) {
-            const int cnt = beg[q + 1] - beg[q];
-            const int ppw = choose_eval_ppw(cnt, groups, par_waves, c->n_cus);
-            const long long gy = (cnt + (long long)par_waves * ppw - 1) / ((long long)par_waves * ppw);
-            fills = groups * gy >= 2LL * c->n_cus;
-        }
-        if (fills) break;
-    }
-    return std::max(1, k);
-}
-
-// One chunk of reports [base, base + n) of a prep_init, in work area W.
-// lc: the frontier cache (or null); on a hit the parents are read from
-// cin (the aggregator's node slot); the last level's nodes go to cout (the
-// spare slot).  tail: the stream of the chunk's last part (finalize, FLP,
-// result and cache copies): the sponge stream when chunks are pipelined (the
-// next chunk's evaluation, in the other half of the work arena, then
-// overlaps this chunk's last sponges), else the main stream.  sev0: first
-// sync event of this chunk (consecutive pipelined chunks use disjoint ones).
+// ---------------------------------------------------------------- prep_init
+// The level kernel of each variant (kernels.hpp eval_aes_body; schedule.hpp
+// LEVEL_VARIANTS lists the legal ones): the launch path and the LDS attribute
+// loop of mastic_ctx_create both go through here.
+typedef void (*LevelKernel)(McParams, Planes, AesArgs);
 template <class F>
-static int run_chunk(mastic_ctx* c, mastic_reports* rep, const Tree* t, const WorkLayout& wl, int agg_id,
-                     size_t base, int n, int stride, size_t& evi, LevelCache* lc, bool hit, const uint32_t* cin,
-                     uint32_t* cout, uint32_t* W, hipStream_t ss, hipStream_t tail, size_t sev0) {
-    const McParams& p = c->p;
-    Planes pl = make_planes(W, wl, n, stride);
-    Result& R = c->res[agg_id];
+static LevelKernel level_kernel(int variant) {
+    switch (variant) {
+    case LV_GEN | LV_FC: return k_eval_aes<F, true, true>;
+    case 0: return k_eval_aes<F, false, false>;
+    case LV_GEN: return k_eval_aes<F, true, false>;
+    case LV_SPLIT: return k_eval_aes<F, false, false, true>;
+    case LV_GEN | LV_SPLIT: return k_eval_aes<F, true, false, true>;
+    case LV_WIDE: return k_eval_aes_wide<F, false>;
+    case LV_WIDE | LV_GEN: return k_eval_aes_wide<F, true>;
+    case LV_WIDE | LV_SPLIT: return k_eval_aes_wide<F, false, true>;
+    case LV_WIDE | LV_GEN | LV_SPLIT: return k_eval_aes_wide<F, true, true>;
+    }
+    return nullptr;
+}
+
+// One chunk of reports [base, base + n) of a prep_init, in work area W, and
+// its launch plan (schedule.hpp plan_chunk), which run() executes step by
+// step.  lc: the frontier cache (or null); on a hit the parents are read from
+// cin (the aggregator's node slot); the last level's nodes go to cout (the
+// spare slot).  ss: the chunk's sponge stream.  tail: the stream of the
+// chunk's last part (finalize, FLP, result and cache copies): the sponge
+// stream when chunks are pipelined (the next chunk's evaluation, in the other
+// half of the work arena, then overlaps this chunk's last sponges), else the
+// main stream.  sev: next sync event of this chunk (consecutive pipelined
+// chunks use disjoint ones); evi: next timing event of the call.
+struct Chunk {
+    mastic_ctx* c;
+    mastic_reports* rep;
+    const Tree* t;
+    const WorkLayout& wl;
+    const ChunkPlan& plan;
+    int agg_id, n, stride;
+    size_t base;
+    uint32_t* W;
+    hipStream_t ss, tail;
+    LevelCache* lc;
+    bool hit;
+    const uint32_t* cin;
+    uint32_t* cout;
+    size_t& evi;
+    size_t sev;
+    Planes pl;
     // A single-chunk call with the frontier cache keeps both binder sponges
     // and the root sum in the cache's planes (same stride): a hit resumes and
     // updates them in place, a miss fills them; no copies in or out.
-    const bool direct = lc && base == 0 && (size_t)n == rep->n && lc->S == (size_t)stride;
-    if (direct) {
-        pl.sp_onehot = lc->sp.as<uint32_t>();
-        pl.sp_payload = lc->sp.as<uint32_t>() + (size_t)50 * lc->S;
-        pl.rootsum = lc->rootsum.as<uint32_t>();
-    }
-    // Every level plane (child seeds, frontier payloads, proof / payload-
-    // difference ring, out shares, staged last-level payloads) is written
-    // before it is read: level l reads only level l-1's nodes / expanded
-    // nodes, which level l-1 wrote, and each candidate prefix is one child of
-    // level L.  So only the per-report header planes (keys, correction words,
-    // sponge states, FLP planes, status) are cleared -- 8 KB per report at C2
-    // instead of the whole 9.7 MB work area (119 GB of fill per C2 step).  A
-    // frontier-cache hit writes every header plane it reads except the
-    // status plane: it clears just that.
-    if (hit)
-        HIPCHK(c, hipMemsetAsync(pl.status, 0, (size_t)stride * 4, c->stream));
-    else {
-        // Of the header, the keys, nonces and correction words (k_unpack: every
-        // report row, every level the call reads) and the AES key schedules and
-        // sponge states (k_setup: every row) are written in full before any
-        // read, so only their padding rows are cleared; the planes between
-        // (leader proof share, seeds: by aggregator and circuit) and from the
-        // root sum on (accumulated root sum and FLP, result and status planes)
-        // are cleared whole.  C2: 409 of 2,107 header words per report.
-        // (work_layout order: key, nonce, cw_* | lps, seed, peer | rk_*, sp_* | rootsum .. status)
-        HIPCHK(c, hipMemsetAsync(W + wl.lps * (size_t)stride, 0, (wl.rk_ext - wl.lps) * (size_t)stride * 4, c->stream));
-        HIPCHK(c, hipMemsetAsync(W + wl.rootsum * (size_t)stride, 0, (wl.cs[0] - wl.rootsum) * (size_t)stride * 4,
-                                 c->stream));
-        if (stride > n)
-            HIPCHK(c, hipMemset2DAsync(W + n, (size_t)stride * 4, 0, (size_t)(stride - n) * 4, wl.lps, c->stream));
-        // level 0 reads its parent (the root) payload from fr_w[1]: zeros
-        HIPCHK(c, hipMemsetAsync(W + wl.fr_w[1] * (size_t)stride, 0, (size_t)p.value_len * p.w32 * stride * 4, c->stream));
-    }
-    const size_t ps = mc_public_share_size(p), is = mc_input_share_size(p, agg_id);
-    const uint8_t* ins = agg_id == 0 ? rep->in0.as<uint8_t>() : rep->in1.as<uint8_t>();
-    const PrefixState* pfx = (const PrefixState*)c->pfx.p;
-    {
+    bool direct;
+    // tiled level buffers (kernels.hpp AbsorbArgs): words per report group
+    // (MASTIC_BINDER_TILED=0: plane layout, i.e. group stride 64, row stride = stride)
+    int oh_gstride, pay_gstride, bin_rstride;
+    int groups() const { return (n + 63) / 64; }  // report groups (rows beyond n are padding)
+    int wlw() const { return c->p.value_len * c->p.w32; }
+    uint32_t* plane(size_t off) const { return W + off * (size_t)stride; }
+    // level binder buffers: the ring slots (with the frontier cache too: a
+    // hit resumes both sponges from their cached states, so no level's
+    // proofs or payload differences outlive the call)
+    uint32_t* oh_buf(int lv) const { return plane(wl.onehot[lv % NSLOT]); }
+    uint32_t* pay_buf(int lv) const { return plane(wl.payload[lv % NSLOT]); }
+    hipStream_t stream(int role) const { return role == ST_MAIN ? c->stream : role == ST_THIRD ? c->stream3 : ss; }
+
+    // Clears the header planes, then k_unpack and the row tiles.
+    int unpack() {
+        const McParams& p = c->p;
+        // Every level plane (child seeds, frontier payloads, proof / payload-
+        // difference ring, out shares, staged last-level payloads) is written
+        // before it is read: level l reads only level l-1's nodes / expanded
+        // nodes, which level l-1 wrote, and each candidate prefix is one child of
+        // level L.  So only the per-report header planes (keys, correction words,
+        // sponge states, FLP planes, status) are cleared -- 8 KB per report at C2
+        // instead of the whole 9.7 MB work area (119 GB of fill per C2 step).  A
+        // frontier-cache hit writes every header plane it reads except the
+        // status plane: it clears just that.
+        if (hit)
+            HIPCHK(c, hipMemsetAsync(pl.status, 0, (size_t)stride * 4, c->stream));
+        else {
+            // Of the header, the keys, nonces and correction words (k_unpack: every
+            // report row, every level the call reads) and the AES key schedules and
+            // sponge states (k_setup: every row) are written in full before any
+            // read, so only their padding rows are cleared; the planes between
+            // (leader proof share, seeds: by aggregator and circuit) and from the
+            // root sum on (accumulated root sum and FLP, result and status planes)
+            // are cleared whole.  C2: 409 of 2,107 header words per report.
+            // (work_layout order: key, nonce, cw_* | lps, seed, peer | rk_*, sp_* | rootsum .. status)
+            HIPCHK(c, hipMemsetAsync(W + wl.lps * (size_t)stride, 0, (wl.rk_ext - wl.lps) * (size_t)stride * 4, c->stream));
+            HIPCHK(c, hipMemsetAsync(W + wl.rootsum * (size_t)stride, 0, (wl.cs[0] - wl.rootsum) * (size_t)stride * 4,
+                                     c->stream));
+            if (stride > n)
+                HIPCHK(c, hipMemset2DAsync(W + n, (size_t)stride * 4, 0, (size_t)(stride - n) * 4, wl.lps, c->stream));
+            // level 0 reads its parent (the root) payload from fr_w[1]: zeros
+            HIPCHK(c, hipMemsetAsync(W + wl.fr_w[1] * (size_t)stride, 0, (size_t)p.value_len * p.w32 * stride * 4, c->stream));
+        }
+        const size_t ps = mc_public_share_size(p), is = mc_input_share_size(p, agg_id);
         const uint8_t* pub = rep->pub.as<uint8_t>() + ps * base;
-        const uint8_t* in_b = ins + is * base;
+        const uint8_t* in_b = (agg_id == 0 ? rep->in0 : rep->in1).as<uint8_t>() + is * base;
         const int l_lo = hit ? t->L - 1 : 0, l_hi = t->L + 1;  // a hit recomputes level L-1's payloads: its CW
         // Rows of >= 16 KB to unpack per report (C4, C5), 8-byte aligned
         // (BITS a multiple of 32): the correction words and the leader proof
@@ -923,7 +781,7 @@ static int run_chunk(mastic_ctx* c, mastic_reports* rep, const Tree* t, const Wo
                            rep->nonces.as<uint8_t>() + 16 * base, pub, in_b, l_lo, l_hi, tiles ? 1 : 0,
                            rep->wire_flags.as<uint8_t>() + base);
         if (tiles) {
-            const int wlw_ = p.value_len * p.w32, nl = l_hi - l_lo;
+            const int wlw_ = wlw(), nl = l_hi - l_lo;
             auto rows = [&](const uint8_t* src, size_t row_bytes, int nwords, uint32_t* dst) {
                 if (nwords <= 0) return;
                 hipLaunchKernelGGL(k_rows_to_planes, dim3((unsigned)((n + 63) / 64), (unsigned)((nwords + 63) / 64)),
@@ -938,394 +796,106 @@ static int run_chunk(mastic_ctx* c, mastic_reports* rep, const Tree* t, const Wo
             if (agg_id == 0) rows(in_b + 16, is, p.proof_len * p.w32, pl.lps);
         }
         HIPCHK(c, hipGetLastError());
+        return 0;
     }
-    const bool whole = base == 0 && (size_t)n == rep->n && W == c->work.p;
-    const bool rk_ok = hit && whole && c->rk.valid && c->rk.rep_id == rep->id && c->rk.rep_gen == rep->generation() &&
-                       c->rk.n == (size_t)n && c->rk.stride == stride && c->rk.W == (const void*)W &&
-                       c->rk.pfx_key == c->pfx_key;
-    if (!rk_ok) {
-        hipLaunchKernelGGL(k_setup, dim3((stride + 255) / 256), dim3(256), 0, c->stream, pl, pfx, hit ? 0 : 1);
-        c->rk.valid = whole;
-        c->rk.rep_id = rep->id;
-        c->rk.rep_gen = rep->generation();
-        c->rk.n = (size_t)n;
-        c->rk.stride = stride;
-        c->rk.W = (const void*)W;
-        c->rk.pfx_key = c->pfx_key;
-    }
-    HIPCHK(c, hipGetLastError());
 
-    const int groups = (n + 63) / 64;  // report groups (rows beyond n are padding)
-    const int wlw = p.value_len * p.w32;
-    int f_oh = c->pfx_f[PFX_ONEHOT], f_pl = c->pfx_f[PFX_PAYLOAD];
-    auto plane = [&](size_t off) { return W + off * (size_t)stride; };
-    // Per level l, on two streams:
-    //   stream   k_eval_aes(l): AES of level l (12 waves per workgroup) and
-    //            the node proofs of level l-1 (4 proof waves per workgroup)
-    //   stream2  k_absorb(l-1): binder sponges over level l-1's proofs and
-    //            payload differences, after eval_aes(l)
-    // so the sponges of one level overlap the evaluation of the next.  The
-    // last level's proofs come from a k_node_proof launch.  Buffers: child
-    // seeds 2 slots; proof / payload 3 slots (eval_aes(l) writes payload(l)
-    // and proofs(l-1), so it waits absorb(l-3)).  Timing: one (eval, proof,
-    // absorb) event triplet per step of the loop below.
-    size_t sev = sev0;
-    std::vector<hipEvent_t> abs_done(t->L + 1);
-    // tiled level buffers (kernels.hpp AbsorbArgs): words per report group
-    // (MASTIC_BINDER_TILED=0: plane layout, i.e. group stride 64, row stride = stride)
-    const int oh_gstride = c->binder_tiled ? t->max_level_nodes * 8 * 64 : 64;
-    const int pay_gstride = c->binder_tiled ? t->max_parents * wlw * 64 : 64;
-    const int bin_rstride = c->binder_tiled ? 64 : stride;
-    // level binder buffers: the ring slots (with the frontier cache too: a
-    // hit resumes both sponges from their cached states, so no level's
-    // proofs or payload differences outlive the call)
-    auto oh_buf = [&](int lv) -> uint32_t* { return plane(wl.onehot[lv % NSLOT]); };
-    auto pay_buf = [&](int lv) -> uint32_t* { return plane(wl.payload[lv % NSLOT]); };
-    auto oh_gs = [&](int) -> int { return oh_gstride; };
-    auto pay_gs = [&](int) -> int { return pay_gstride; };
-    // Sponges which0 .. which0 + nwh - 1 (0 one-hot, 1 payload) of level lv on
-    // stream `as` after `ready`; *done marks their end.  With `piece`, only a
-    // contiguous piece of the level's messages (a parent range of a segmented
-    // last level): the proofs of its nodes, the payload differences of its
-    // parents.  The fill positions carry across pieces as across levels.
-    struct Piece {
-        int node0, nodes;      // one-hot sponge: nodes [node0, node0 + nodes) of the level
-        int parent0, parents;  // payload sponge: parents [parent0, parent0 + parents)
-    };
-    const bool pair = c->absorb_mode == 2 || (c->absorb_mode == 0 && (size_t)n < c->absorb_single_min);
-    const bool wide = pair && c->eval_wide;  // the level kernel may take 104 VGPRs (k_eval_aes_wide)
-    auto launch_sponges = [&](int lv, int which0, int nwh, hipEvent_t ready, hipEvent_t e4, hipEvent_t e5,
-                              hipStream_t as, hipEvent_t* done, const Piece* piece = nullptr) -> int {
-        const Piece whole{0, 2 * t->n_parents[lv], 0, t->n_parents[lv]};
-        const Piece& pc = piece ? *piece : whole;
-        AbsorbArgs ab;
-        ab.which0 = which0;
-        ab.seg[0] = oh_buf(lv) + (size_t)pc.node0 * 8 * bin_rstride;
-        ab.gstride[0] = oh_gs(lv);
-        ab.nbytes[0] = pc.nodes * 32;
-        ab.f[0] = f_oh;
-        ab.seg[1] = pay_buf(lv) + (size_t)pc.parent0 * wlw * bin_rstride;
-        ab.gstride[1] = pay_gs(lv);
-        ab.rstride = bin_rstride;
-        ab.nbytes[1] = lv > 0 ? pc.parents * wlw * 4 : 0;
-        ab.f[1] = f_pl;
-        ab.prio = c->absorb_prio;
-        ab.dbg = c->absorb_dbg;
-        if (as != c->stream) HIPCHK(c, hipStreamWaitEvent(as, ready, 0));
-        if (e4) HIPCHK(c, hipEventRecord(e4, as));
-        if (c->dbg_skip & 4) {
-            // timing experiments only: no binder sponges (results wrong)
-        } else if (pair)
-            hipLaunchKernelGGL(k_absorb_pair,
-                               dim3((groups * 64 * 2 + c->absorb_threads - 1) / c->absorb_threads, (unsigned)nwh),
-                               dim3(c->absorb_threads), c->absorb_lds, as, pl, ab);
-        else
-            hipLaunchKernelGGL(k_absorb, dim3((groups * 64 + 255) / 256, (unsigned)nwh), dim3(256), c->absorb_lds, as,
-                               pl, ab);
-        if (e5) HIPCHK(c, hipEventRecord(e5, as));
-        HIPCHK(c, hipGetLastError());
-        *done = get_sync_event(c, sev++);
-        HIPCHK(c, hipEventRecord(*done, as));
-        // measurement schedule (mastic_set_serial_sponges): the main stream waits
-        // for this launch, so it runs alone on the chip (standalone sponge rate)
-        if (c->serial_sponges && as != c->stream) HIPCHK(c, hipStreamWaitEvent(c->stream, *done, 0));
-        if (which0 == 0) f_oh = (f_oh + ab.nbytes[0]) % KECCAK_RATE;
-        if (which0 + nwh > 1) f_pl = (f_pl + ab.nbytes[1]) % KECCAK_RATE;
-        return 0;
-    };
-    // both sponges of level lv (the default schedule)
-    std::vector<hipEvent_t> pl_done(t->L + 1, nullptr);  // split schedule: payload sponge of each level
-    auto launch_absorb = [&](int lv, hipEvent_t ready, hipEvent_t e4, hipEvent_t e5, hipStream_t as) -> int {
-        return launch_sponges(lv, 0, 2, ready, e4, e5, as, &abs_done[lv]);
-    };
-    // Split schedule (single-chunk misses, MASTIC_SPLIT_SPONGES): level l's
-    // payload differences are complete after eval(l), so its payload sponge
-    // starts then, on the third stream, while its one-hot sponge still waits
-    // for level l's node proofs (eval(l+1)'s proof waves).  The payload chain
-    // -- the long one at C4 / C5 -- then runs a level earlier and leaves a
-    // shorter tail after the last level.
-    // Measured (profiles/r04_v23_ab_split_sponges.txt): C5 +1.4 %, C4 +0.6 %,
-    // C2 -0.5 %, c2sweep -0.9 % -- so by default for Field128 only, whose
-    // payload messages (VALUE_LEN x 16 B per parent) make that chain long.
-    const bool split_on = c->split_sponges < 0 ? p.field == 128 : c->split_sponges > 0;
-    const bool split = split_on && !hit && tail == c->stream && ss == c->stream2;
-    // cache planes <-> work planes of this chunk (columns base .. base + n)
-    auto from_cache = [&](uint32_t* dst, const uint32_t* src, size_t planes) -> int {
-        HIPCHK(c, hipMemcpy2DAsync(dst, (size_t)stride * 4, src + base, lc->S * 4, (size_t)n * 4, planes,
-                                   hipMemcpyDeviceToDevice, c->stream));
-        return 0;
-    };
-    auto to_cache = [&](uint32_t* dst, const uint32_t* src, size_t planes) -> int {
-        HIPCHK(c, hipMemcpy2DAsync(dst + base, lc->S * 4, src, (size_t)stride * 4, (size_t)n * 4, planes,
-                                   hipMemcpyDeviceToDevice, tail));
-        return 0;
-    };
-    if (hit && !direct) {
-        // levels 0..L-1 from the cache.  The binder messages are BFS-ordered
-        // (mastic.py:263-275), so the cached call's message is a prefix of
-        // this one's: both sponges resume from their states at the end of the
-        // cached call (mid-block, unpadded; k_finalize pads a register copy).
-        if (from_cache(pl.sp_onehot, lc->sp.as<uint32_t>(), 50)) return -1;
-        if (from_cache(pl.sp_payload, lc->sp.as<uint32_t>() + (size_t)50 * lc->S, 50)) return -1;
-        // the root sum of the cached level-0 evaluation (counter check)
-        if (from_cache(pl.rootsum, lc->rootsum.as<uint32_t>(), (size_t)wlw)) return -1;
-    }
-    if (hit) {
-        // (no timing events for the cached levels: nothing is launched for
-        // them, and 6 records per level cost ~1.4 ms of host time at L = 255)
-        for (int lv = 0; lv < t->L; lv++) {
-            f_oh = (f_oh + 2 * t->n_parents[lv] * 32) % KECCAK_RATE;
-            f_pl = (f_pl + (lv > 0 ? t->n_parents[lv] * wlw * 4 : 0)) % KECCAK_RATE;
+    // k_setup (AES key schedules, sponge states) unless the arena still holds
+    // this batch's (mastic_ctx::rk); a hit's sponge states and root sum from the cache.
+    int setup() {
+        const bool whole = base == 0 && (size_t)n == rep->n && W == c->work.p;
+        const bool rk_ok = hit && whole && c->rk.valid && c->rk.rep_id == rep->id &&
+                           c->rk.rep_gen == rep->generation() && c->rk.n == (size_t)n && c->rk.stride == stride &&
+                           c->rk.W == (const void*)W && c->rk.pfx_key == c->pfx_key;
+        if (!rk_ok) {
+            hipLaunchKernelGGL(k_setup, dim3((stride + 255) / 256), dim3(256), 0, c->stream, pl,
+                               (const PrefixState*)c->pfx.p, hit ? 0 : 1);
+            c->rk = {whole, rep->id, rep->generation(), (size_t)n, stride, (const void*)W, c->pfx_key};
         }
+        HIPCHK(c, hipGetLastError());
+        if (hit && !direct) {
+            // levels 0..L-1 from the cache (its planes' columns base .. base + n).
+            // The binder messages are BFS-ordered (mastic.py:263-275), so the
+            // cached call's message is a prefix of this one's: both sponges resume
+            // from their states at the end of the cached call (mid-block,
+            // unpadded; k_finalize pads a register copy); and the root sum of the
+            // cached level-0 evaluation (counter check).
+            auto from_cache = [&](uint32_t* dst, const uint32_t* src, size_t planes) {
+                return hipMemcpy2DAsync(dst, (size_t)stride * 4, src + base, lc->S * 4, (size_t)n * 4, planes,
+                                        hipMemcpyDeviceToDevice, c->stream);
+            };
+            HIPCHK(c, from_cache(pl.sp_onehot, lc->sp.as<uint32_t>(), 50));
+            HIPCHK(c, from_cache(pl.sp_payload, lc->sp.as<uint32_t>() + (size_t)50 * lc->S, 50));
+            HIPCHK(c, from_cache(pl.rootsum, lc->rootsum.as<uint32_t>(), (size_t)wlw()));
+        }
+        return 0;
     }
-    // the last level's node proofs in the level kernel (after each workgroup's
-    // parents) instead of a k_node_proof launch: cache hits, and with
-    // MASTIC_FUSE_PROOFS=2 cache-on misses too (whole parents only)
-    // A miss's last level is fused too when the frontier cache is on (the
-    // sweeps: c2sweep +1 %, its level kernels -4 %), not without it (C2 -1.7 %,
-    // C5 -0.9 %: the FC kernel's 128 VGPRs leave no room for the previous
-    // level's sponge waves beside it; profiles/r04_v21_ab_fused_last_miss.txt)
-    const bool fuse_last = hit ? c->fuse_proofs >= 1
-                               : ((lc && (c->fuse_proofs == 2 || (c->fuse_proofs >= 1 && c->fuse_last_miss_fc))) ||
-                                  (c->fuse_last_miss && c->fuse_proofs >= 1));
-    // The last level's sponges: on the main stream for a hit that runs as one
-    // chunk (nothing to overlap them with: the next work on the main stream
-    // needs them; the cross-stream event round trip cost ~0.08 ms per call),
-    // else on the sponge stream after the level's earlier sponges.
-    const hipStream_t last_as = (hit && tail == c->stream && c->hit_absorb_main) ? c->stream : ss;
-    // Segmented last level (mastic_set_last_level_segments): a miss with no
-    // frontier cache, not pipelined, beside the 2-lane sponges.  Level L's
-    // parents (BFS order, as are both binder messages) are cut into nseg
-    // contiguous ranges, one level-kernel launch each.  The proof waves of
-    // range 0 take level L-1's node proofs as ever; those of range q >= 1 the
-    // proofs of level L's nodes of range q-1 (from cs_out, which the previous
-    // launch wrote); k_node_proof is left with the last range's nodes.  The
-    // sponges follow piece by piece -- payload piece q after launch q, one-hot
-    // piece q-1 after launch q -- so that what remains after the last level
-    // kernel is one range's proofs and sponge pieces instead of a level and a
-    // half of them.  Every other call keeps one launch per level.
-    const int L_ = t->L;
-    int nseg = 1;
-    if (!lc && !hit && tail == c->stream && ss == c->stream2 && pair && !fuse_last) {
-        const int par_waves = c->par_waves > 0 ? c->par_waves : EVAL_WAVES - c->proof_waves;
-        nseg = last_level_segments(c, t, groups, par_waves);
-    }
-    // Levels L-1 and L then run the split form whatever the field: pay(L-1)
-    // is complete after eval(L-1), so it goes to the third stream at once
-    // (after absorb(L-2), which holds the payload sponge's previous piece)
-    // instead of waiting, paired with oh(L-1), for eval(L)'s first proofs.
-    const bool seg_early = nseg > 1 && c->seg_early_payload && !split && L_ >= 2;
-    const std::vector<int> seg_beg = segment_ranges(c, t, nseg);
-    // timing marks of a sponge piece that has no level-kernel launch of its
-    // own: an event sextuple whose kernel pairs are empty
-    auto piece_marks = [&](hipStream_t as, hipEvent_t* e4, hipEvent_t* e5) -> int {
-        for (int i = 0; i < 4; i++) HIPCHK(c, hipEventRecord(get_event(c, evi++), as));
+
+    // One timing sextuple [aes0, aes1, proof0, proof1, absorb0, absorb1] of a
+    // step (mastic_last_timing3 decodes strides of six): the first four are
+    // recorded here on stream s, with `kernel` launched inside pair `slot`
+    // (0 aes, 1 proof; -1: no kernel, both pairs empty); the absorb pair goes to
+    // the step's sponge launch.
+    template <class Fn>
+    int timed_step(hipStream_t s, int slot, Fn&& kernel, hipEvent_t* e4, hipEvent_t* e5) {
+        for (int i = 0; i < 4; i++) {
+            HIPCHK(c, hipEventRecord(get_event(c, evi++), s));
+            if (i == 2 * slot) kernel();
+            if (i == 2 * slot + 1) HIPCHK(c, hipGetLastError());
+        }
         *e4 = get_event(c, evi++);
         *e5 = get_event(c, evi++);
         return 0;
-    };
-    // One level-kernel launch (a whole level, or one parent range of a
-    // segmented last level) on the main stream.
-    auto launch_level = [&](const AesArgs& a, dim3 grid, int l, bool fuse) {
-        // the frontier-cache variant only where its features are used: the
-        // last level (convert seeds staged for the cache) and a hit (parent
-        // payloads recomputed, fused proofs); a miss's other levels run the
-        // plain kernel (the variant's uniform branches and extra spills cost
-        // a few per cent)
-        if ((lc && (hit || l == t->L || c->fc_all)) || fuse)
-            hipLaunchKernelGGL((k_eval_aes<F, true, true>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES, c->stream,
-                               p, pl, a);
-        // beside the 2-lane sponges (96 VGPRs) the plain variants take 104
-        // (k_eval_aes_wide); beside k_absorb (128) they keep 96
-        else if (wide && a.split > 1 && l == 0)
-            hipLaunchKernelGGL((k_eval_aes_wide<F, true, true>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES,
-                               c->stream, p, pl, a);
-        else if (wide && a.split > 1)
-            hipLaunchKernelGGL((k_eval_aes_wide<F, false, true>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES,
-                               c->stream, p, pl, a);
-        else if (wide && (l == 0 || l == t->L))
-            hipLaunchKernelGGL((k_eval_aes_wide<F, true>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES, c->stream,
-                               p, pl, a);
-        else if (wide)
-            hipLaunchKernelGGL((k_eval_aes_wide<F, false>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES, c->stream,
-                               p, pl, a);
-        else if (a.split > 1 && l == 0)
-            hipLaunchKernelGGL((k_eval_aes<F, true, false, true>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES,
-                               c->stream, p, pl, a);
-        else if (a.split > 1)
-            hipLaunchKernelGGL((k_eval_aes<F, false, false, true>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES,
-                               c->stream, p, pl, a);
-        else if (l == 0 || l == t->L)
-            hipLaunchKernelGGL((k_eval_aes<F, true, false>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES, c->stream,
-                               p, pl, a);
-        else
-            hipLaunchKernelGGL((k_eval_aes<F, false, false>), grid, dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES, c->stream,
-                               p, pl, a);
-    };
-    for (int l = hit ? t->L : 0; l <= t->L; l++) {
-        const int np_ = t->n_parents[l];
-        if (!hit && l >= NSLOT) {
-            HIPCHK(c, hipStreamWaitEvent(c->stream, abs_done[l - NSLOT], 0));
-            if (split && pl_done[l - NSLOT]) HIPCHK(c, hipStreamWaitEvent(c->stream, pl_done[l - NSLOT], 0));
+    }
+
+    // The planned sponges [sp0, sp1) of a step whose end `ready` marks, each on
+    // its stream after `ready`; (e4, e5): the absorb pair of the step's timing
+    // sextuple.  Their ends are marked in c->sp_done.  The fill positions carry
+    // across pieces as across levels (the plan tracks them).
+    int launch_sponges(int sp0, int sp1, hipEvent_t ready, hipEvent_t e4, hipEvent_t e5) {
+        for (int i = sp0; i < sp1; i++) {
+            const SpongeLaunch& s = plan.sponges[i];
+            const hipStream_t as = stream(s.stream);
+            // the sponge's previous piece ran on another stream
+            if (s.prev >= 0) HIPCHK(c, hipStreamWaitEvent(as, c->sp_done[s.prev], 0));
+            hipEvent_t m4 = s.marks == MK_STEP ? e4 : nullptr, m5 = s.marks == MK_STEP ? e5 : nullptr;
+            // a sponge piece that has no level-kernel launch of its own: an event
+            // sextuple whose kernel pairs are empty
+            if (s.marks == MK_PIECE && timed_step(as, -1, [] {}, &m4, &m5)) return MASTIC_EHIP;
+            AbsorbArgs ab;
+            ab.which0 = s.which0;
+            ab.seg[0] = oh_buf(s.level) + (size_t)s.piece.node0 * 8 * bin_rstride;
+            ab.gstride[0] = oh_gstride;
+            ab.nbytes[0] = s.piece.nodes * 32;
+            ab.f[0] = s.f_oh;
+            ab.seg[1] = pay_buf(s.level) + (size_t)s.piece.parent0 * wlw() * bin_rstride;
+            ab.gstride[1] = pay_gstride;
+            ab.rstride = bin_rstride;
+            ab.nbytes[1] = s.level > 0 ? s.piece.parents * wlw() * 4 : 0;
+            ab.f[1] = s.f_pl;
+            ab.prio = c->absorb_prio;
+            ab.dbg = c->absorb_dbg;
+            if (as != c->stream) HIPCHK(c, hipStreamWaitEvent(as, ready, 0));
+            if (m4) HIPCHK(c, hipEventRecord(m4, as));
+            if (c->k.dbg_skip & 4) {
+                // timing experiments only: no binder sponges (results wrong)
+            } else if (plan.pair)
+                hipLaunchKernelGGL(k_absorb_pair,
+                                   dim3((groups() * 64 * 2 + c->absorb_threads - 1) / c->absorb_threads, (unsigned)s.nwh),
+                                   dim3(c->absorb_threads), c->absorb_lds, as, pl, ab);
+            else
+                hipLaunchKernelGGL(k_absorb, dim3((groups() * 64 + 255) / 256, (unsigned)s.nwh), dim3(256),
+                                   c->absorb_lds, as, pl, ab);
+            if (m5) HIPCHK(c, hipEventRecord(m5, as));
+            HIPCHK(c, hipGetLastError());
+            const hipEvent_t done = c->sp_done[i] = get_sync_event(c, sev++);
+            HIPCHK(c, hipEventRecord(done, as));
+            // measurement schedule (mastic_set_serial_sponges): the main stream waits
+            // for this launch, so it runs alone on the chip (standalone sponge rate)
+            if (c->serial_sponges && as != c->stream) HIPCHK(c, hipStreamWaitEvent(c->stream, done, 0));
+            for (int w = s.which0; w < s.which0 + s.nwh; w++) (w ? c->pl_done : c->oh_done)[s.level] = done;
         }
-        AesArgs a;
-        a.level = l;
-        a.agg_id = agg_id;
-        a.n_parents = np_;
-        // items per workgroup: par_waves x ppw, par_waves = the AES waves (the
-        // proof waves mop up after their proofs).  MASTIC_PAR_WAVES=16 hands
-        // all waves parents from the start: measured neutral on C4 and C2 and
-        // 3 % slower on C5 (profiles/r02_v12_ab_level_kernel.json)
-        const int par_waves = c->par_waves > 0 ? c->par_waves : EVAL_WAVES - c->proof_waves;
-        // small levels: parents split into block-range items (AesArgs::split);
-        // not at the last level (out shares, frontier-cache staging) nor on a hit
-        a.split = 1;
-        a.split_blocks = 0;
-        {
-            const int epb = p.field == 64 ? 2 : 1;
-            const int nblk = (p.value_len + epb - 1) / epb;
-            a.split_blocks = nblk;
-            // (<= 32 parents: their pass-0 flags live in the workgroup's sync words)
-            if (!hit && l < t->L && c->small_split && np_ <= 32 && !(c->dbg_skip & 2))
-                choose_split(np_, l > 0 ? t->n_parents[l - 1] : 0, c->proof_waves, nblk, &a.split,
-                             &a.split_blocks);
-        }
-        const int n_items = np_ * a.split;
-        a.ppw = choose_eval_ppw(n_items, groups, par_waves, c->n_cus);
-        // a split level keeps all items of a report group in one workgroup
-        // (the fix-up pass needs every item of a parent stored): gy = 1
-        if (a.split > 1) a.ppw = (n_items + par_waves - 1) / par_waves;
-        a.parent_node = t->d_parent + t->poff[l];
-        a.child_exp = t->d_exp + t->off[l];
-        a.child_pfx = t->d_pfx + t->off[l];
-        a.cs_in = hit ? cin + base : plane(wl.cs[(l + 1) & 1]);
-        a.cs_out = plane(wl.cs[l & 1]);
-        a.fr_w_in = plane(wl.fr_w[(l + 1) & 1]);
-        a.in_stride = hit ? (int)lc->S : stride;
-        a.fr_w_out = plane(wl.fr_w[l & 1]);
-        a.payload = pay_buf(l);
-        a.out = R.out.as<uint32_t>() + base;  // columns base .. base + n of the result planes
-        a.out_stride = (int)R.stride;
-        a.force_slow_blk = c->force_slow_blk;
-        // frontier cache: stage this level's convert seeds (last level); on a
-        // hit recompute the parents' payloads from the cached ones into the
-        // (otherwise unused) parent-payload planes
-        a.cache_out = (lc && l == t->L) ? cout + base : nullptr;
-        a.cache_stride = lc ? (int)lc->S : 0;
-        a.wp_buf = plane(wl.fr_w[(l + 1) & 1]);
-        a.recompute_wp = hit ? 1 : 0;
-        const bool fuse = fuse_last && l == t->L;
-        a.fuse_proofs = fuse ? (c->fuse_proofs == 3 ? 3 : 1) : 0;
-        a.cur_path_bytes = (l + 1 + 7) / 8;
-        a.cur_child_path = t->d_path + t->off[l] * 8;
-        a.cur_onehot = oh_buf(l);
-        a.aes_waves = EVAL_WAVES - c->proof_waves;
-        if (fuse && a.fuse_proofs == 1)
-            a.aes_waves = EVAL_WAVES - (hit ? hit_proof_waves(p, c) : miss_proof_waves(p, c, t->n_parents[l - 1 < 0 ? 0 : l - 1],
-                                                                                      np_, l > 0));
-        a.par_waves = par_waves;
-        a.proof_prio = c->proof_prio;
-        a.aes_prio = c->aes_prio;
-        a.dbg_skip = c->dbg_skip;
-        const int gy = (n_items + a.par_waves * a.ppw - 1) / (a.par_waves * a.ppw);
-        a.pv_level = l - 1;
-        a.pv_nodes = (l > 0 && !hit) ? 2 * t->n_parents[l - 1] : 0;  // hit: level L-1's proofs are cached
-        const int pw = EVAL_WAVES - a.aes_waves;  // proof waves of this launch
-        a.pv_npw = (a.pv_nodes + gy * pw - 1) / (gy * pw);
-        a.pv_path_bytes = (l + 7) / 8;
-        a.pv_child_path = l > 0 ? t->d_path + t->off[l - 1] * 8 : nullptr;
-        a.pv_onehot = l > 0 ? oh_buf(l - 1) : nullptr;
-        a.pv_cs = a.cs_in;
-        a.oh_gstride = l > 0 ? oh_gs(l - 1) : oh_gstride;
-        a.pay_gstride = pay_gs(l);
-        a.bin_rstride = bin_rstride;
-        a.np = (const PrefixState*)c->pfx.p + PFX_NODE;
-        a.np_f = c->pfx_f[PFX_NODE];
-        if (nseg > 1 && l == L_) {
-            // the segmented last level: one launch per parent range
-            for (int q = 0; q < nseg; q++) {
-                const int p0 = seg_beg[q], cnt = seg_beg[q + 1] - p0;
-                AesArgs b = a;
-                b.n_parents = cnt;
-                b.ppw = choose_eval_ppw(cnt, groups, par_waves, c->n_cus);
-                b.parent_node = a.parent_node + p0;
-                b.child_exp = a.child_exp + 2 * (size_t)p0;
-                b.child_pfx = a.child_pfx + 2 * (size_t)p0;
-                b.cur_child_path = a.cur_child_path + 2 * (size_t)p0 * 8;
-                // by child node / parent ordinal of the range: planes of the
-                // work buffer, rows of the (tiled) payload-difference buffer
-                b.cs_out = a.cs_out + 2 * (size_t)p0 * 5 * stride;
-                b.fr_w_in = a.fr_w_in + (size_t)p0 * wlw * stride;
-                b.payload = a.payload + (size_t)p0 * wlw * bin_rstride;
-                if (q > 0) {
-                    // proofs of level L's nodes of range q-1 (the previous launch's cs_out)
-                    const size_t n0 = 2 * (size_t)seg_beg[q - 1];
-                    b.pv_level = l;
-                    b.pv_nodes = 2 * (p0 - seg_beg[q - 1]);
-                    b.pv_path_bytes = (l + 1 + 7) / 8;
-                    b.pv_child_path = t->d_path + (t->off[l] + n0) * 8;
-                    b.pv_onehot = oh_buf(l) + n0 * 8 * bin_rstride;
-                    b.pv_cs = a.cs_out + n0 * 5 * stride;
-                    b.oh_gstride = oh_gs(l);
-                }
-                const int gyq = (cnt + b.par_waves * b.ppw - 1) / (b.par_waves * b.ppw);
-                b.pv_npw = (b.pv_nodes + gyq * pw - 1) / (gyq * pw);
-                hipEvent_t e0 = get_event(c, evi++), e1 = get_event(c, evi++);
-                hipEvent_t e2 = get_event(c, evi++), e3 = get_event(c, evi++);
-                hipEvent_t e4 = get_event(c, evi++), e5 = get_event(c, evi++);
-                HIPCHK(c, hipEventRecord(e0, c->stream));
-                launch_level(b, dim3(groups, gyq), l, false);
-                HIPCHK(c, hipEventRecord(e1, c->stream));
-                HIPCHK(c, hipGetLastError());
-                HIPCHK(c, hipEventRecord(e2, c->stream));
-                HIPCHK(c, hipEventRecord(e3, c->stream));
-                hipEvent_t aes_done = get_sync_event(c, sev++);
-                HIPCHK(c, hipEventRecord(aes_done, c->stream));
-                // the one-hot piece whose proofs this launch made ...
-                if (q > 0) {
-                    const Piece pc{2 * seg_beg[q - 1], 2 * (p0 - seg_beg[q - 1]), 0, 0};
-                    if (launch_sponges(l, 0, 1, aes_done, e4, e5, ss, &abs_done[l], &pc)) return -1;
-                } else if (split || seg_early) {
-                    if (launch_sponges(l - 1, 0, 1, aes_done, e4, e5, ss, &abs_done[l - 1])) return -1;
-                } else {
-                    // both sponges of level L-1; the payload sponge moves to the third stream after it
-                    if (launch_absorb(l - 1, aes_done, e4, e5, ss)) return -1;
-                    HIPCHK(c, hipStreamWaitEvent(c->stream3, abs_done[l - 1], 0));
-                }
-                // ... and this range's payload piece
-                hipEvent_t p4, p5;
-                if (piece_marks(c->stream3, &p4, &p5)) return -1;
-                const Piece pp{0, 0, p0, cnt};
-                if (launch_sponges(l, 1, 1, aes_done, p4, p5, c->stream3, &pl_done[l], &pp)) return -1;
-            }
-            continue;
-        }
-        dim3 grid(groups, gy);
-        hipEvent_t e0 = get_event(c, evi++), e1 = get_event(c, evi++);
-        hipEvent_t e2 = get_event(c, evi++), e3 = get_event(c, evi++);
-        hipEvent_t e4 = get_event(c, evi++), e5 = get_event(c, evi++);
-        HIPCHK(c, hipEventRecord(e0, c->stream));
-        launch_level(a, grid, l, fuse);
-        HIPCHK(c, hipEventRecord(e1, c->stream));
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipEventRecord(e2, c->stream));
-        HIPCHK(c, hipEventRecord(e3, c->stream));
-        hipEvent_t aes_done = get_sync_event(c, sev++);
-        HIPCHK(c, hipEventRecord(aes_done, c->stream));
-        if (split && l > 0) {
-            // payload(l) now, one-hot(l-1) after the proofs this launch made
-            if (launch_sponges(l, 1, 1, aes_done, e4, e5, c->stream3, &pl_done[l])) return -1;
-            if (launch_sponges(l - 1, 0, 1, aes_done, nullptr, nullptr, ss, &abs_done[l - 1])) return -1;
-        } else if (l > 0 && !hit) {
-            if (launch_absorb(l - 1, aes_done, e4, e5, ss)) return -1;
-            if (seg_early && l == L_ - 1) {
-                // pay(L-1) is complete: on the third stream, after pay(L-2) in the launch above
-                hipEvent_t p4, p5;
-                HIPCHK(c, hipStreamWaitEvent(c->stream3, abs_done[l - 1], 0));
-                if (piece_marks(c->stream3, &p4, &p5)) return -1;
-                if (launch_sponges(l, 1, 1, aes_done, p4, p5, c->stream3, &pl_done[l])) return -1;
-            }
-        } else {
+        if (sp0 == sp1) {
+            // no sponge follows (level 0 of a miss, a hit's level kernel): empty marks
             if (c->sponge_delay_us > 0) {
                 // test hook: the sponge stream is still busy when these (empty)
                 // marks are recorded there; nothing on the main stream waits for them
@@ -1338,108 +908,214 @@ static int run_chunk(mastic_ctx* c, mastic_reports* rep, const Tree* t, const Wo
             HIPCHK(c, hipEventRecord(e4, ss));
             HIPCHK(c, hipEventRecord(e5, ss));
         }
+        return 0;
     }
-    if (fuse_last) {
-        // the last level's proofs came from the level kernel's AES waves: its sponges
+
+    // One planned level-kernel launch (a whole level, or one parent range of a
+    // segmented last level) on the main stream: the pointers of AesArgs from the
+    // launch's level, parent range and proof job.
+    template <class F>
+    void launch_level(const LevelLaunch& v) {
+        const int l = v.level, wlw = this->wlw();
+        const size_t p0 = (size_t)v.p0;
+        uint32_t* cs_level = plane(wl.cs[l & 1]);
+        AesArgs a;
+        a.level = l;
+        a.agg_id = agg_id;
+        a.n_parents = v.cnt;
+        a.split = v.split;
+        a.split_blocks = v.split_blocks;
+        a.ppw = v.ppw;
+        a.parent_node = t->d_parent + t->poff[l] + p0;
+        a.child_exp = t->d_exp + t->off[l] + 2 * p0;
+        a.child_pfx = t->d_pfx + t->off[l] + 2 * p0;
+        // by child node / parent ordinal of the range: planes of the work
+        // buffer, rows of the (tiled) payload-difference buffer
+        a.cs_in = hit ? cin + base : plane(wl.cs[(l + 1) & 1]);
+        a.cs_out = cs_level + 2 * p0 * 5 * stride;
+        a.fr_w_in = plane(wl.fr_w[(l + 1) & 1]) + p0 * wlw * stride;
+        a.in_stride = hit ? (int)lc->S : stride;
+        a.fr_w_out = plane(wl.fr_w[l & 1]);
+        a.payload = pay_buf(l) + p0 * wlw * bin_rstride;
+        a.out = c->res[agg_id].out.as<uint32_t>() + base;  // columns base .. base + n of the result planes
+        a.out_stride = (int)c->res[agg_id].stride;
+        a.force_slow_blk = c->force_slow_blk;
+        // frontier cache: stage this level's convert seeds (last level); on a
+        // hit recompute the parents' payloads from the cached ones into the
+        // (otherwise unused) parent-payload planes
+        a.cache_out = (lc && l == t->L) ? cout + base : nullptr;
+        a.cache_stride = lc ? (int)lc->S : 0;
+        a.wp_buf = plane(wl.fr_w[(l + 1) & 1]);
+        a.recompute_wp = hit ? 1 : 0;
+        a.fuse_proofs = v.fuse_proofs;
+        a.cur_path_bytes = (l + 1 + 7) / 8;
+        a.cur_child_path = t->d_path + (t->off[l] + 2 * p0) * 8;
+        a.cur_onehot = oh_buf(l);
+        a.aes_waves = v.aes_waves;
+        a.par_waves = v.par_waves;
+        a.proof_prio = c->proof_prio;
+        a.aes_prio = c->aes_prio;
+        a.dbg_skip = c->k.dbg_skip;
+        // the proof job: level l-1's nodes (seeds in cs_in), or an earlier range
+        // of this level's (the previous launch's cs_out)
+        const size_t n0 = (size_t)v.pv_node0;
+        a.pv_level = v.pv_level;
+        a.pv_nodes = v.pv_nodes;
+        a.pv_npw = v.pv_npw;
+        a.pv_path_bytes = (v.pv_level + 1 + 7) / 8;
+        a.pv_child_path = v.pv_level >= 0 ? t->d_path + (t->off[v.pv_level] + n0) * 8 : nullptr;
+        a.pv_onehot = v.pv_level >= 0 ? oh_buf(v.pv_level) + n0 * 8 * bin_rstride : nullptr;
+        a.pv_cs = v.pv_level == l ? cs_level + n0 * 5 * stride : a.cs_in;
+        a.oh_gstride = oh_gstride;
+        a.pay_gstride = pay_gstride;
+        a.bin_rstride = bin_rstride;
+        a.np = (const PrefixState*)c->pfx.p + PFX_NODE;
+        a.np_f = c->pfx_f[PFX_NODE];
+        hipLaunchKernelGGL(level_kernel<F>(v.variant), dim3(groups(), v.gy), dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES,
+                           c->stream, c->p, pl, a);
+    }
+
+    // The planned launches in order: each level kernel on the main stream, then
+    // its sponges; then the final step (the last level's remaining node proofs,
+    // or marks only) and its sponges.  Timing: one event sextuple per step.
+    template <class F>
+    int run_plan() {
+        c->sp_done.assign(plan.sponges.size(), nullptr);
+        c->oh_done.assign(t->L + 1, nullptr);
+        c->pl_done.assign(t->L + 1, nullptr);
+        hipEvent_t e4, e5;
+        for (const LevelLaunch& v : plan.launches) {
+            if (v.wait_level >= 0) {
+                // proof / payload ring of NSLOT slots: this launch overwrites that level's
+                const hipEvent_t oh = c->oh_done[v.wait_level], pay = c->pl_done[v.wait_level];
+                HIPCHK(c, hipStreamWaitEvent(c->stream, oh, 0));
+                if (pay && pay != oh) HIPCHK(c, hipStreamWaitEvent(c->stream, pay, 0));
+            }
+            if (int rc = timed_step(c->stream, 0, [&] { launch_level<F>(v); }, &e4, &e5)) return rc;
+            hipEvent_t aes_done = get_sync_event(c, sev++);
+            HIPCHK(c, hipEventRecord(aes_done, c->stream));
+            if (int rc = launch_sponges(v.sp0, v.sp1, aes_done, e4, e5)) return rc;
+        }
         const int l = t->L;
-        hipEvent_t e0 = get_event(c, evi++), e1 = get_event(c, evi++);
-        hipEvent_t e2 = get_event(c, evi++), e3 = get_event(c, evi++);
-        hipEvent_t e4 = get_event(c, evi++), e5 = get_event(c, evi++);
-        HIPCHK(c, hipEventRecord(e0, c->stream));
-        HIPCHK(c, hipEventRecord(e1, c->stream));
-        HIPCHK(c, hipEventRecord(e2, c->stream));
-        HIPCHK(c, hipEventRecord(e3, c->stream));
-        hipEvent_t np_done = get_sync_event(c, sev++);
-        HIPCHK(c, hipEventRecord(np_done, c->stream));
-        if (split ? launch_sponges(l, 0, 1, np_done, e4, e5, last_as, &abs_done[l])
-                  : launch_absorb(l, np_done, e4, e5, last_as))
-            return -1;
-    } else {
-        // the last level's node proofs, then its sponges
-        // (a segmented last level: the last range's; the level kernels made the others)
-        const int l = t->L;
-        const int n0 = 2 * seg_beg[nseg - 1];
-        const int nn = 2 * t->n_parents[l] - n0;
         ProofArgs pa;
         pa.level = l;
-        pa.n_nodes = nn;
-        pa.npw = choose_ppw(nn, groups);
+        pa.n_nodes = plan.final_nn;
+        pa.npw = plan.final_npw;
         pa.path_bytes = (l + 1 + 7) / 8;
-        pa.child_path = t->d_path + (t->off[l] + (size_t)n0) * 8;
-        pa.cs = plane(wl.cs[l & 1]) + (size_t)n0 * 5 * stride;
-        pa.onehot = oh_buf(l) + (size_t)n0 * 8 * bin_rstride;
-        pa.oh_gstride = oh_gs(l);
+        pa.child_path = t->d_path + (t->off[l] + (size_t)plan.final_n0) * 8;
+        pa.cs = plane(wl.cs[l & 1]) + (size_t)plan.final_n0 * 5 * stride;
+        pa.onehot = oh_buf(l) + (size_t)plan.final_n0 * 8 * bin_rstride;
+        pa.oh_gstride = oh_gstride;
         pa.bin_rstride = bin_rstride;
         pa.np = (const PrefixState*)c->pfx.p + PFX_NODE;
         pa.f = c->pfx_f[PFX_NODE];
-        hipEvent_t e0 = get_event(c, evi++), e1 = get_event(c, evi++);
-        hipEvent_t e2 = get_event(c, evi++), e3 = get_event(c, evi++);
-        hipEvent_t e4 = get_event(c, evi++), e5 = get_event(c, evi++);
-        HIPCHK(c, hipEventRecord(e0, c->stream));
-        HIPCHK(c, hipEventRecord(e1, c->stream));
-        HIPCHK(c, hipEventRecord(e2, c->stream));
-        hipLaunchKernelGGL(k_node_proof, dim3(groups, (nn + 4 * pa.npw - 1) / (4 * pa.npw)), dim3(256), 0,
-                           c->stream, p, pl, pa);
-        HIPCHK(c, hipEventRecord(e3, c->stream));
-        HIPCHK(c, hipGetLastError());
+        auto node_proofs = [&] {
+            hipLaunchKernelGGL(k_node_proof, dim3(groups(), (pa.n_nodes + 4 * pa.npw - 1) / (4 * pa.npw)), dim3(256), 0,
+                               c->stream, c->p, pl, pa);
+        };
+        // (a fused last level: its proofs came from the level kernel's AES waves)
+        if (int rc = timed_step(c->stream, plan.fuse_last ? -1 : 1, node_proofs, &e4, &e5)) return rc;
         hipEvent_t np_done = get_sync_event(c, sev++);
         HIPCHK(c, hipEventRecord(np_done, c->stream));
-        const Piece pc{n0, nn, 0, 0};
-        if (nseg > 1 ? launch_sponges(l, 0, 1, np_done, e4, e5, last_as, &abs_done[l], &pc)
-            : split  ? launch_sponges(l, 0, 1, np_done, e4, e5, last_as, &abs_done[l])
-                     : launch_absorb(l, np_done, e4, e5, last_as))
-            return -1;
+        const int n_sponges = (int)plan.sponges.size();  // the last one is the final step's
+        return launch_sponges(n_sponges - 1, n_sponges, np_done, e4, e5);
     }
-    hipEvent_t flp_done = nullptr;
-    if (t->weight_check) {
-        // The FLP randomness and query (mastic.py:234-256) read only header
-        // planes and level 0's root sum: on their own stream once the last
-        // level kernel is done, beside the last level's sponges (a few
-        // latency-bound chains that leave most of the chip idle: C5's last
-        // payload chain runs ~34 ms) instead of after them.  (Right after
-        // level 0 they slowed the level kernels beside them by as much as
-        // they saved: C4 -1.8 %, profiles/r05_v36_ab_flp_side_stream.txt.)
-        hipEvent_t lv_done = get_sync_event(c, sev++);
-        HIPCHK(c, hipEventRecord(lv_done, c->stream));
-        HIPCHK(c, hipStreamWaitEvent(c->stream4, lv_done, 0));
-        FlpArgs fl{agg_id, t->L};
-        hipLaunchKernelGGL(k_flp_rand<F>, dim3((stride + 255) / 256), dim3(256), 0, c->stream4, p, pl, fl, pfx);
-        hipLaunchKernelGGL(k_flp_query<F>, dim3((stride + 255) / 256), dim3(256), 0, c->stream4, p, pl,
-                           flp_consts<F>(p));
-        HIPCHK(c, hipGetLastError());
-        flp_done = get_sync_event(c, sev++);
-        HIPCHK(c, hipEventRecord(flp_done, c->stream4));
-    }
-    if (tail != last_as) HIPCHK(c, hipStreamWaitEvent(tail, abs_done[t->L], 0));
-    if (pl_done[t->L]) HIPCHK(c, hipStreamWaitEvent(tail, pl_done[t->L], 0));  // split schedule, segmented last level
-    FinalArgs fa{agg_id, f_oh, f_pl};
-    hipLaunchKernelGGL(k_finalize<F>, dim3((stride + 255) / 256), dim3(256), 0, tail, p, pl, fa, pfx);
-    HIPCHK(c, hipGetLastError());
-    // the status, verifier and joint-rand planes copied below are the FLP's
-    if (flp_done) HIPCHK(c, hipStreamWaitEvent(tail, flp_done, 0));
-    if (lc && !direct) {
-        // frontier cache for the next level (the last level's nodes are in the
-        // spare slot already, written by its level kernel): the root sum
-        if (!hit && to_cache(lc->rootsum.as<uint32_t>(), pl.rootsum, (size_t)wlw)) return -1;
-        // both sponges after levels 0..L (stream waited for abs_done[L] above)
-        if (to_cache(lc->sp.as<uint32_t>(), pl.sp_onehot, 50)) return -1;
-        if (to_cache(lc->sp.as<uint32_t>() + (size_t)50 * lc->S, pl.sp_payload, 50)) return -1;
-    }
-    // results -> the agg_id slot (plane stride = all reports; the level
-    // kernel wrote the out shares there)
-    int rc = 0;
-    rc |= copy_planes(c, R.eval_proof, R.stride, base, pl.eval_proof, stride, n, 8, tail);
-    rc |= copy_planes(c, R.status, R.stride, base, (const uint32_t*)pl.status, stride, n, 1, tail);
-    if (t->weight_check) {
-        rc |= copy_planes(c, R.verifier, R.stride, base, pl.verifier, stride, n, (size_t)p.verifier_len * p.w32,
-                          tail);
-        if (p.joint_rand_len > 0) {
-            rc |= copy_planes(c, R.jr_part, R.stride, base, pl.jr_part, stride, n, 8, tail);
-            rc |= copy_planes(c, R.jr_seed, R.stride, base, pl.jr_seed, stride, n, 8, tail);
+
+    // FLP side stream, k_finalize, then the cache and result copies on the tail stream.
+    template <class F>
+    int finish() {
+        const McParams& p = c->p;
+        const PrefixState* pfx = (const PrefixState*)c->pfx.p;
+        hipEvent_t flp_done = nullptr;
+        if (t->weight_check) {
+            // The FLP randomness and query (mastic.py:234-256) read only header
+            // planes and level 0's root sum: on their own stream once the last
+            // level kernel is done, beside the last level's sponges (a few
+            // latency-bound chains that leave most of the chip idle: C5's last
+            // payload chain runs ~34 ms) instead of after them.  (Right after
+            // level 0 they slowed the level kernels beside them by as much as
+            // they saved: C4 -1.8 %, profiles/r05_v36_ab_flp_side_stream.txt.)
+            hipEvent_t lv_done = get_sync_event(c, sev++);
+            HIPCHK(c, hipEventRecord(lv_done, c->stream));
+            HIPCHK(c, hipStreamWaitEvent(c->stream4, lv_done, 0));
+            FlpArgs fl{agg_id, t->L};
+            hipLaunchKernelGGL(k_flp_rand<F>, dim3((stride + 255) / 256), dim3(256), 0, c->stream4, p, pl, fl, pfx);
+            hipLaunchKernelGGL(k_flp_query<F>, dim3((stride + 255) / 256), dim3(256), 0, c->stream4, p, pl,
+                               flp_consts<F>(p));
+            HIPCHK(c, hipGetLastError());
+            flp_done = get_sync_event(c, sev++);
+            HIPCHK(c, hipEventRecord(flp_done, c->stream4));
         }
+        // the tail follows the last piece of either sponge
+        const hipEvent_t oh = c->oh_done[t->L], pay = c->pl_done[t->L];
+        if (tail != stream(plan.last_stream)) HIPCHK(c, hipStreamWaitEvent(tail, oh, 0));
+        if (pay && pay != oh) HIPCHK(c, hipStreamWaitEvent(tail, pay, 0));  // split schedule, segmented last level
+        FinalArgs fa{agg_id, plan.f_oh, plan.f_pl};
+        hipLaunchKernelGGL(k_finalize<F>, dim3((stride + 255) / 256), dim3(256), 0, tail, p, pl, fa, pfx);
+        HIPCHK(c, hipGetLastError());
+        // the status, verifier and joint-rand planes copied below are the FLP's
+        if (flp_done) HIPCHK(c, hipStreamWaitEvent(tail, flp_done, 0));
+        if (lc && !direct) {
+            // work planes of this chunk -> cache planes (columns base .. base + n)
+            auto to_cache = [&](uint32_t* dst, const uint32_t* src, size_t planes) {
+                return hipMemcpy2DAsync(dst + base, lc->S * 4, src, (size_t)stride * 4, (size_t)n * 4, planes,
+                                        hipMemcpyDeviceToDevice, tail);
+            };
+            // frontier cache for the next level (the last level's nodes are in the
+            // spare slot already, written by its level kernel): the root sum
+            if (!hit) HIPCHK(c, to_cache(lc->rootsum.as<uint32_t>(), pl.rootsum, (size_t)wlw()));
+            // both sponges after levels 0..L (the tail waited for them above)
+            HIPCHK(c, to_cache(lc->sp.as<uint32_t>(), pl.sp_onehot, 50));
+            HIPCHK(c, to_cache(lc->sp.as<uint32_t>() + (size_t)50 * lc->S, pl.sp_payload, 50));
+        }
+        // results -> the agg_id slot (plane stride = all reports; the level
+        // kernel wrote the out shares there)
+        Result& R = c->res[agg_id];
+        int rc = 0;
+        rc |= copy_planes(c, R.eval_proof, R.stride, base, pl.eval_proof, stride, n, 8, tail);
+        rc |= copy_planes(c, R.status, R.stride, base, (const uint32_t*)pl.status, stride, n, 1, tail);
+        if (t->weight_check) {
+            rc |= copy_planes(c, R.verifier, R.stride, base, pl.verifier, stride, n, (size_t)p.verifier_len * p.w32,
+                              tail);
+            if (p.joint_rand_len > 0) {
+                rc |= copy_planes(c, R.jr_part, R.stride, base, pl.jr_part, stride, n, 8, tail);
+                rc |= copy_planes(c, R.jr_seed, R.stride, base, pl.jr_seed, stride, n, 8, tail);
+            }
+        }
+        return rc;
     }
-    return rc;
-}
+
+    // Runs one chunk: unpack, key setup, the planned launches, finish.  The plan
+    // also says how many sync and timing events the chunk takes: prep_init spaces
+    // pipelined chunks' sync events by the former, and mastic_last_timing3
+    // decodes the latter in strides of six, so a step that consumed another
+    // number than planned is an error here, not a miscount there.  The check
+    // is a tripwire for a plan and an executor that have drifted apart: it runs
+    // after the chunk's work is queued, so it cannot keep a pipelined chunk
+    // that overran its range from sharing sync events with its neighbour, only
+    // fail the call (whose results are then never marked ready).  The C ABI has
+    // no code for an internal error; MASTIC_EHIP with this text is the nearest.
+    template <class F>
+    int run() {
+        const size_t evi0 = evi, sev0 = sev;
+        pl = make_planes(W, wl, n, stride);
+        direct = lc && base == 0 && (size_t)n == rep->n && lc->S == (size_t)stride;
+        if (direct) {
+            pl.sp_onehot = lc->sp.as<uint32_t>();
+            pl.sp_payload = lc->sp.as<uint32_t>() + (size_t)50 * lc->S;
+            pl.rootsum = lc->rootsum.as<uint32_t>();
+        }
+        oh_gstride = c->binder_tiled ? t->max_level_nodes * 8 * 64 : 64;
+        pay_gstride = c->binder_tiled ? t->max_parents * wlw() * 64 : 64;
+        bin_rstride = c->binder_tiled ? 64 : stride;
+        int rc = unpack();
+        if (rc || (rc = setup()) || (rc = run_plan<F>()) || (rc = finish<F>())) return rc;
+        if (evi - evi0 != (size_t)plan.n_timing || sev - sev0 != (size_t)plan.n_sync)
+            return fail(c, MASTIC_EHIP, "chunk used %zu timing and %zu sync events, its plan says %d and %d",
+                        evi - evi0, sev - sev0, plan.n_timing, plan.n_sync);
+        return 0;
+    }
+};
 
 static uint64_t default_budget(mastic_ctx* c) {
     if (c->budget) return c->budget;
@@ -1648,29 +1324,29 @@ extern "C" int mastic_prep_init(mastic_ctx* c, mastic_reports* rep, const uint8_
     const bool pipe = c->chunk_pipeline && n > chunk && chunk >= 128 && half_cap >= pad + 64;
     if (pipe) chunk = std::min(capped ? chunk : chunk / 2, half_cap - pad) / 64 * 64;
     const size_t half = c->work.bytes / 2 / 4 / 64 * 64;  // words: second half's offset
-    // sync events one chunk uses (a segmented last level: three per parent range)
-    const size_t nsev = 3 * (size_t)t->L + 12 +
-                        3 * (size_t)std::min(std::max(c->last_level_segments, LAST_LEVEL_SEGMENTS_AUTO), t->n_parents[t->L]);
+    // the launch plans (schedule.hpp) of a full chunk and, if shorter, of the last one
+    const size_t n_full = std::min(chunk, n), n_last = n - (n - 1) / chunk * chunk;
+    ChunkPlan* plans[2] = {&c->plans[0], &c->plans[n_last != n_full]};
+    for (int i = 0; i <= (n_last != n_full); i++)
+        plan_chunk(c->k, p, *t, (int)(i ? n_last : n_full), hit, lc != nullptr, pipe, c->pfx_f[PFX_ONEHOT],
+                   c->pfx_f[PFX_PAYLOAD], plans[i]);
+    // sync events one chunk uses: pipelined chunks alternate between two disjoint ranges of them
+    const size_t nsev = (size_t)std::max(plans[0]->n_sync, plans[1]->n_sync);
     size_t evi = 0;
     hipEvent_t t0 = get_event(c, evi++), t1 = get_event(c, evi++);
     HIPCHK(c, hipEventRecord(t0, c->stream));
     hipEvent_t half_free[2] = {get_sync_event(c, 2 * nsev), get_sync_event(c, 2 * nsev + 1)};
-    size_t k = 0;
-    for (size_t b = 0; b < n; b += chunk, k++) {
-        const int nn = (int)std::min(chunk, n - b);
-        const int stride = (int)(round_up(nn, 64) + pad);
+    for (size_t b = 0, k = 0; b < n; b += chunk, k++) {
+        const int nn = (int)std::min(chunk, n - b), stride = (int)(round_up(nn, 64) + pad);
         const int h = pipe ? (int)(k & 1) : 0;
         if (pipe && k >= 2) HIPCHK(c, hipStreamWaitEvent(c->stream, half_free[h], 0));
         uint32_t* W = c->work.as<uint32_t>() + h * half;
         // pipelined chunks alternate between two sponge streams: a chunk's
         // sponges must not queue behind the previous chunk's trailing ones
-        hipStream_t ss = (pipe && h) ? c->stream3 : c->stream2;
-        hipStream_t tail = pipe ? ss : c->stream;
-        rc = p.field == 64
-                 ? run_chunk<F64>(c, rep, t, wl, agg_id, b, nn, stride, evi, lc, hit, cin, cout, W, ss, tail,
-                                  h * nsev)
-                 : run_chunk<F128>(c, rep, t, wl, agg_id, b, nn, stride, evi, lc, hit, cin, cout, W, ss, tail,
-                                   h * nsev);
+        hipStream_t ss = (pipe && h) ? c->stream3 : c->stream2, tail = pipe ? ss : c->stream;
+        Chunk ck{c, rep, t, wl, *plans[b + chunk >= n], agg_id, nn, stride, b, W, ss, tail, lc, hit, cin, cout, evi,
+                 h * nsev};
+        rc = p.field == 64 ? ck.run<F64>() : ck.run<F128>();
         if (rc) {
             if (lc) lc->drop();
             return rc;
@@ -1835,7 +1511,7 @@ static int aggregate_impl(mastic_ctx* c, int agg_id, const uint8_t* valid, uint3
     // few rows over many reports (a sweep level: ~700 rows x 1M reports):
     // split the reports into chunks so the grid fills the chip, then merge
     // the chunks' partial sums mod p (k_fold_shares)
-    const size_t target = (size_t)c->n_cus * 16;
+    const size_t target = (size_t)c->k.n_cus * 16;
     size_t chunks = 1;
     if (rows < target && R.n >= 8192)
         chunks = std::min<size_t>({(target + rows - 1) / rows, R.n / 4096, (size_t)1024});
@@ -2839,7 +2515,7 @@ extern "C" int mastic_ctx_create(const mastic_params* up, mastic_ctx** out) {
     c->user = *up;
     c->p = p;
     c->device = up->device;
-    c->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    c->k.n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     {
         int khz = 0;
         if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, up->device) == hipSuccess && khz > 0)
@@ -2851,13 +2527,13 @@ extern "C" int mastic_ctx_create(const mastic_params* up, mastic_ctx** out) {
     // MASTIC_DBG_SKIP and MASTIC_ABSORB_DBG skip or gut kernels: results wrong.
     {
         const char* e = getenv("MASTIC_ABSORB_SINGLE");
-        if (e) c->absorb_mode = e[0] == '1' ? 1 : (e[0] == '2' ? 2 : 0);
+        if (e) c->k.absorb_mode = e[0] == '1' ? 1 : (e[0] == '2' ? 2 : 0);
         const char* esm = getenv("MASTIC_ABSORB_SINGLE_MIN");
-        if (esm) c->absorb_single_min = (size_t)std::max(0, atoi(esm));
+        if (esm) c->k.absorb_single_min = (size_t)std::max(0, atoi(esm));
         const char* l = getenv("MASTIC_ABSORB_LDS_KB");
         c->absorb_lds = l ? std::max(0, std::min(160, atoi(l))) * 1024 : 0;
         const char* pw = getenv("MASTIC_PROOF_WAVES");
-        if (pw) c->proof_waves = std::max(1, std::min(15, atoi(pw)));
+        if (pw) c->k.proof_waves = std::max(1, std::min(15, atoi(pw)));
         const char* spd = getenv("MASTIC_STRIDE_PAD");
         if (spd) c->stride_pad = std::max(0, std::min(1 << 20, atoi(spd))) / 64 * 64;
         const char* wa = getenv("MASTIC_WORK_ARENA_GB");
@@ -2871,97 +2547,61 @@ extern "C" int mastic_ctx_create(const mastic_params* up, mastic_ctx** out) {
         const char* adb = getenv("MASTIC_ABSORB_DBG");
         if (adb) c->absorb_dbg = atoi(adb);
         const char* dsk = getenv("MASTIC_DBG_SKIP");
-        if (dsk) c->dbg_skip = atoi(dsk);
+        if (dsk) c->k.dbg_skip = atoi(dsk);
         const char* xp = getenv("MASTIC_AES_PRIO");
         if (xp) c->aes_prio = std::max(0, std::min(2, atoi(xp)));
         const char* pp = getenv("MASTIC_PROOF_PRIO");
         if (pp) c->proof_prio = std::max(0, std::min(2, atoi(pp)));
         const char* pw2 = getenv("MASTIC_PAR_WAVES");
-        if (pw2) c->par_waves = std::max(1, std::min(EVAL_WAVES, atoi(pw2)));
+        if (pw2) c->k.par_waves = std::max(1, std::min(EVAL_WAVES, atoi(pw2)));
         const char* cp = getenv("MASTIC_CHUNK_PIPELINE");
         if (cp) c->chunk_pipeline = cp[0] != '0';
         const char* hpw = getenv("MASTIC_HIT_PROOF_WAVES");
-        if (hpw) c->hit_proof_waves = std::max(0, std::min(15, atoi(hpw)));
+        if (hpw) c->k.hit_proof_waves = std::max(0, std::min(15, atoi(hpw)));
         const char* fp = getenv("MASTIC_FUSE_PROOFS");
-        if (fp) c->fuse_proofs = std::max(0, std::min(3, atoi(fp)));
+        if (fp) c->k.fuse_proofs = std::max(0, std::min(3, atoi(fp)));
         const char* fa = getenv("MASTIC_FC_ALL");
-        if (fa) c->fc_all = fa[0] == '1';
+        if (fa) c->k.fc_all = fa[0] == '1';
         const char* cr = getenv("MASTIC_CHUNK_REPORTS");
         if (cr) c->chunk_max = (size_t)std::max(0, atoi(cr));
         const char* spl = getenv("MASTIC_SPLIT_SPONGES");
-        if (spl) c->split_sponges = spl[0] == '1' ? 1 : 0;
+        if (spl) c->k.split_sponges = spl[0] == '1' ? 1 : 0;
         const char* flm = getenv("MASTIC_FUSE_LAST_MISS");
-        if (flm) c->fuse_last_miss = flm[0] == '1';
+        if (flm) c->k.fuse_last_miss = flm[0] == '1';
         const char* flf = getenv("MASTIC_FUSE_LAST_MISS_FC");
-        if (flf) c->fuse_last_miss_fc = flf[0] != '0';
+        if (flf) c->k.fuse_last_miss_fc = flf[0] != '0';
         const char* ham = getenv("MASTIC_HIT_ABSORB_MAIN");
-        if (ham) c->hit_absorb_main = ham[0] != '0';
+        if (ham) c->k.hit_absorb_main = ham[0] != '0';
         const char* ssp = getenv("MASTIC_SMALL_SPLIT");
-        if (ssp) c->small_split = ssp[0] != '0';
+        if (ssp) c->k.small_split = ssp[0] != '0';
         const char* evw = getenv("MASTIC_EVAL_WIDE");
-        if (evw) c->eval_wide = evw[0] != '0';
+        if (evw) c->k.eval_wide = evw[0] != '0';
         const char* tnw = getenv("MASTIC_DBG_TIMING_NOWAIT");  // the round-5 last_timing bug, for its test's A/B
         if (tnw) c->timing_nowait = tnw[0] == '1';
         const char* ssr = getenv("MASTIC_SERIAL_SPONGES");
         if (ssr) c->serial_sponges = ssr[0] == '1';
         const char* lls = getenv("MASTIC_LAST_LEVEL_SEGMENTS");
-        if (lls) c->last_level_segments = std::max(0, atoi(lls));
+        if (lls) c->k.last_level_segments = std::max(0, atoi(lls));
         const char* sge = getenv("MASTIC_SEG_EARLY");
-        if (sge) c->seg_early_payload = sge[0] != '0';
+        if (sge) c->k.seg_early_payload = sge[0] != '0';
         const char* sgb = getenv("MASTIC_SEG_BALANCE");
-        if (sgb) c->seg_balance = sgb[0] != '0';
+        if (sgb) c->k.seg_balance = sgb[0] != '0';
     }
 #endif
     // the level kernel's LDS (table + key schedules) is dynamic, above the
-    // 64 KiB default
-    if (hipFuncSetAttribute((const void*)k_eval_aes<F64, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            EVAL_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_eval_aes<F128, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            EVAL_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_eval_aes<F64, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            EVAL_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_eval_aes<F128, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            EVAL_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_eval_aes<F64, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            EVAL_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_eval_aes<F128, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            EVAL_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_eval_aes<F64, true, false, true>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, EVAL_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_eval_aes<F64, false, false, true>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, EVAL_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_eval_aes<F128, true, false, true>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, EVAL_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_eval_aes<F128, false, false, true>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, EVAL_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_eval_aes_wide<F64, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            EVAL_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_eval_aes_wide<F128, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            EVAL_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_eval_aes_wide<F64, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            EVAL_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_eval_aes_wide<F128, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            EVAL_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_eval_aes_wide<F64, true, true>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, EVAL_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_eval_aes_wide<F64, false, true>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, EVAL_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_eval_aes_wide<F128, true, true>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, EVAL_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_eval_aes_wide<F128, false, true>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, EVAL_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_absorb_pair, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
-            hipSuccess ||
-        hipFuncSetAttribute((const void*)k_absorb, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
-            hipSuccess) {
-        delete c;
-        return MASTIC_EHIP;
-    }
+    // 64 KiB default: every variant the plan may launch, of both fields
+    auto lds = [](const void* fn, int bytes) {
+        return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
+    };
+    bool attrs = lds((const void*)k_absorb_pair, 160 * 1024) && lds((const void*)k_absorb, 160 * 1024);
+    for (int v : LEVEL_VARIANTS)
+        attrs = attrs && lds((const void*)level_kernel<F64>(v), EVAL_LDS_BYTES) &&
+                lds((const void*)level_kernel<F128>(v), EVAL_LDS_BYTES);
     // the binder sponges are the latency-critical chain: their stream gets the
     // highest priority so their workgroups are dispatched first
     int prio_lo = 0, prio_hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
+    if (!attrs || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, prio_hi) != hipSuccess ||
         hipStreamCreateWithPriority(&c->stream3, hipStreamNonBlocking, prio_hi) != hipSuccess ||
         hipStreamCreateWithFlags(&c->stream4, hipStreamNonBlocking) != hipSuccess) {
@@ -3028,8 +2668,8 @@ extern "C" int mastic_set_serial_sponges(mastic_ctx* c, int on) {
 
 extern "C" int mastic_set_last_level_segments(mastic_ctx* c, int k) {
     if (!c || k < 0) return MASTIC_EINVAL;
-    const int prev = c->last_level_segments;
-    c->last_level_segments = k;
+    const int prev = c->k.last_level_segments;
+    c->k.last_level_segments = k;
     return prev;
 }
 

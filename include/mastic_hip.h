@@ -306,8 +306,9 @@ int mastic_set_serial_sponges(mastic_ctx* ctx, int on);
  * k = 0: chosen by the library (1 for a level too small to fill the device
  * twice per range); k >= 1: forced, at most one range per parent.  Every other
  * call (frontier cache on, pipelined chunks, one-lane sponges) keeps one
- * launch per level.  Results are identical for every k.  Returns the previous
- * setting or MASTIC_EINVAL. */
+ * launch per level (csrc/schedule.hpp plan_chunk decides, last_level_segments
+ * and segment_ranges cut the level).  Results are identical for every k.
+ * Returns the previous setting or MASTIC_EINVAL. */
 int mastic_set_last_level_segments(mastic_ctx* ctx, int k);
 /* Wait for all enqueued work of the ctx. */
 int mastic_synchronize(mastic_ctx* ctx);
