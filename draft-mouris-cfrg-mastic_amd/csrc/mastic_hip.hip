@@ -27,6 +27,7 @@
 #include "comm_agree.hpp"
 #include "host_tree.hpp"
 #include "kernels.hpp"
+#include "memplan.hpp"
 #include "schedule.hpp"
 #include "shard.hpp"
 
@@ -123,8 +124,6 @@ struct Result {
     DevBuf out, eval_proof, verifier, jr_part, jr_seed, status;
 };
 
-inline size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
-
 // Frontier cache of one aggregator (mastic_set_frontier_cache; SURVEY.md §8f
 // row 1).  In a level sweep (examples.py:37-91) prep_init at level L evaluates
 // the whole tree again, but its levels 0..L-1 are usually exactly the previous
@@ -140,19 +139,11 @@ inline size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
 // shared by the ctx's aggregators (mastic_ctx::fc_spare; a hit reads its
 // parents from this aggregator's slot meanwhile), and the call then swaps the
 // two: three node slots in all, no copy of the level into the cache.
-struct LevelCache {
-    bool valid = false;
-    uint64_t rep_id = 0, rep_gen = 0;  // the batch (mastic_reports::id) and its contents generation
-    size_t n = 0;
-    size_t S = 0;                               // plane stride (n rounded up to 64, plus padding)
-    std::vector<uint8_t> key;                   // u8(len) || verify key || ctx
-    int L = -1;                                 // level of the cached call
-    std::vector<int> n_parents;                 // per level 0..L
-    std::vector<uint32_t> paths;                // child paths of level L (8 words per node)
-    DevBuf sp, rootsum;                         // both binder sponges (2 x 50 planes); root sum (wl planes)
-    DevBuf nd;                                  // last level's nodes [node][5]: convert seed, control bit
-    size_t nodes_cap = 0;                       // nodes nd can hold
-    void drop() { valid = false; }
+// The host metadata (what was cached, the hit test) is memplan.hpp FrontierMeta.
+struct LevelCache : FrontierMeta {
+    DevBuf sp, rootsum;    // both binder sponges (2 x 50 planes); root sum (wl planes)
+    DevBuf nd;             // last level's nodes [node][5]: convert seed, control bit
+    size_t nodes_cap = 0;  // nodes nd can hold
     void release() {
         drop();
         sp.release();
@@ -206,7 +197,7 @@ struct mastic_ctx {
     void comm_release();                       // teardown of a live communicator (defined with the RCCL binding)
     PrefixState pfx_host[PFX_COUNT];
     std::string err;
-    uint64_t budget = 0;
+    MemKnobs m;      // the knobs the memory plan reads (memplan.hpp)
     DevBuf work;     // per-chunk planes
     DevBuf pfx;      // PrefixState[PFX_COUNT]
     DevBuf pfx_bytes, pfx_meta;
@@ -222,11 +213,6 @@ struct mastic_ctx {
     int absorb_lds = 0;         // bytes of dynamic LDS per absorb workgroup (MASTIC_ABSORB_LDS_KB)
     int proof_prio = 0;                  // s_setprio of the level kernel's proof waves (MASTIC_PROOF_PRIO)
     int aes_prio = 0;                    // s_setprio of the AES waves (MASTIC_AES_PRIO)
-    int stride_pad = 64;                 // words of padding per plane row (MASTIC_STRIDE_PAD)
-    size_t work_arena = (size_t)48 << 30;  // minimum size of a new work buffer (MASTIC_WORK_ARENA_GB)
-    // ... with the frontier cache on (level sweeps, whose trees grow from level to level): large
-    // enough that a 1M-report C2 sweep's cache misses run as one chunk (r02 v58: -4 % sweep time)
-    size_t work_arena_fc = (size_t)128 << 30;
     bool binder_tiled = true;            // tiled level binder buffers (MASTIC_BINDER_TILED=0: planes)
     int absorb_threads = 256;            // threads per binder-sponge workgroup (MASTIC_ABSORB_THREADS)
     int absorb_prio = 3;                 // s_setprio of the binder sponge waves (MASTIC_ABSORB_PRIO)
@@ -250,8 +236,6 @@ struct mastic_ctx {
         return hipStreamSynchronize(stream) == hipSuccess && hipStreamSynchronize(stream2) == hipSuccess &&
                hipStreamSynchronize(stream3) == hipSuccess && hipStreamSynchronize(stream4) == hipSuccess;
     }
-    size_t chunk_max = 0;        // reports per chunk cap (0 = what fits; MASTIC_CHUNK_REPORTS)
-    bool chunk_pipeline = true;  // several chunks: two halves of the work arena (MASTIC_CHUNK_PIPELINE=0: off)
     int pfx_f[PFX_COUNT] = {0};  // fill position of each prefix state (host copy)
     std::vector<uint8_t> pfx_key;  // verify key || ctx of the prefix states in pfx (empty: none)
     std::map<std::vector<uint8_t>, Tree*> trees;
@@ -284,6 +268,35 @@ struct mastic_ctx {
     void bury() {
         for (void* q : graveyard) (void)hipFree(q);
         graveyard.clear();
+    }
+    // Give up a buffer that queued kernels may still read: it is freed at the
+    // next idle point of the streams (bury), not here, where hipFree would
+    // wait for the whole device, i.e. for the other aggregator's queued call.
+    void retire(DevBuf& b) {
+        if (b.p && b.own) graveyard.push_back(b.p);
+        b.p = nullptr;
+        b.bytes = 0;
+    }
+    // How reclaim_ensure recovers (memory plan: which differences are deliberate).
+    struct Reclaim {
+        bool inject;       // the attempt consumes fail_allocs (the test hook covers results and cache slots)
+        bool arena;        // the recovery also releases the work arena, and with it the key schedules (rk)
+        bool retry_first;  // the retry tries `first` again before `want`
+        bool if_buried;    // recover only if the graveyard holds something to free
+    };
+    // Allocate b: `first` bytes (0: none), else `want`.  If that fails, wait
+    // for the streams, free the retired buffers (and what `how` adds), and
+    // try once more.
+    bool reclaim_ensure(DevBuf& b, size_t first, size_t want, const Reclaim& how) {
+        auto attempt = [&](bool with_first) { return (with_first && b.ensure(first)) || b.ensure(want); };
+        if (!(how.inject && inject_alloc_failure()) && attempt(first != 0)) return true;
+        if ((how.if_buried && graveyard.empty()) || !idle()) return false;
+        bury();
+        if (how.arena) {
+            work.release();
+            rk.valid = false;
+        }
+        return attempt(first != 0 && how.retry_first);
     }
     // timing
     // timing events and results of the last prep_init of each aggregator
@@ -545,10 +558,7 @@ static int build_tree(mastic_ctx* c, const uint8_t* enc, size_t len, Tree** out)
         // buffers are retired (freed at the next idle point of the ctx's
         // streams, mastic_ctx::bury), not freed here
         for (auto& kv : c->trees) {
-            DevBuf& b = kv.second->dev;
-            if (b.p && b.own) c->graveyard.push_back(b.p);
-            b.p = nullptr;
-            b.bytes = 0;
+            c->retire(kv.second->dev);
             delete kv.second;
         }
         c->trees.clear();
@@ -1117,13 +1127,124 @@ struct Chunk {
     }
 };
 
-static uint64_t default_budget(mastic_ctx* c) {
-    if (c->budget) return c->budget;
+// Free HBM now (none: the query failed).
+static std::optional<size_t> free_hbm() {
     size_t freeb = 0, total = 0;
-    if (hipMemGetInfo(&freeb, &total) != hipSuccess) return 1ull << 30;
-    // work buffers are the only large allocation (C2: ~8.6 MB per report);
-    // one chunk per batch keeps one binder-sponge chain per prep_init
-    return (uint64_t)(freeb * 0.75);
+    if (hipMemGetInfo(&freeb, &total) != hipSuccess) return std::nullopt;
+    return freeb;
+}
+
+static uint64_t default_budget(mastic_ctx* c) {
+    return default_budget(c->m, c->m.budget ? std::nullopt : free_hbm());
+}
+
+// Results and cache slots: HBM is held by the work arena (sized to the budget
+// when the results were smaller) and by retired buffers, so the recovery frees
+// both; the arena is re-allocated afterwards, within what is left (a
+// 2M-report sweep's out shares reach 32 GB per aggregator).
+static constexpr mastic_ctx::Reclaim RECLAIM_ALL{true, true, false, false};
+// The work arena itself: only the retired buffers (cache slots, evicted trees) can make room.
+static constexpr mastic_ctx::Reclaim RECLAIM_BURIED{false, false, true, true};
+
+// The result buffers of a call over n reports.  One that must grow retires the
+// old buffer (mastic_ctx::retire) and allocates with headroom, like DevBuf::grow.
+static int size_results(mastic_ctx* c, Result& R, const Tree* t, size_t n) {
+    const McParams& p = c->p;
+    R.ready = false;
+    R.n = n;
+    R.stride = round_up(std::max<size_t>(n, 1), 64);
+    R.weight_check = t->weight_check;
+    R.n_prefixes = t->n_prefixes;
+    const size_t S = R.stride;
+    auto rgrow = [&](DevBuf& d, size_t want) {
+        if (want <= d.bytes && d.p) return true;
+        const size_t old = d.bytes;
+        c->retire(d);
+        d.own = true;
+        return c->reclaim_ensure(d, std::max(want, old + old / 2), want, RECLAIM_ALL);
+    };
+    if (!rgrow(R.eval_proof, S * 8 * 4) || !rgrow(R.status, S * 4) ||
+        !rgrow(R.out, S * 4 * std::max<size_t>(1, (size_t)t->n_prefixes * (1 + p.output_len) * p.w32)) ||
+        !rgrow(R.verifier, S * 4 * (size_t)p.verifier_len * p.w32) || !rgrow(R.jr_part, S * 32) ||
+        !rgrow(R.jr_seed, S * 32))
+        return fail(c, MASTIC_ENOMEM, "out of device memory (results for %zu reports)", n);
+    HIPCHK(c, hipMemsetAsync(R.jr_part.p, 0, S * 32, c->stream));
+    HIPCHK(c, hipMemsetAsync(R.jr_seed.p, 0, S * 32, c->stream));
+    return 0;
+}
+
+// What a call does with the frontier cache.
+struct CacheUse {
+    LevelCache* lc = nullptr;       // null: the call evaluates without the cache
+    bool hit = false;               // it evaluates only its last level
+    const uint32_t* cin = nullptr;  // a hit's parents: this aggregator's node slot
+    uint32_t* cout = nullptr;       // the last level's nodes: the spare node slot
+};
+
+// Frontier cache (tiled binder buffers only): decide hit / miss and size the
+// slots.  Runs before the work arena is sized, so the HBM budget sees the cache.
+static CacheUse cache_slots(mastic_ctx* c, int agg_id, const Tree* t, const mastic_reports* rep,
+                            const std::vector<uint8_t>& lkey) {
+    CacheUse u;
+    if (!c->frontier_cache || !c->binder_tiled) {
+        c->lc[agg_id].drop();
+        return u;
+    }
+    LevelCache* lc = &c->lc[agg_id];
+    const size_t S1 = round_up(rep->n, 64) + (size_t)c->m.stride_pad;
+    u.hit = frontier_hit(*lc, *t, rep->id, rep->generation(), rep->n, S1, lkey);
+    if (lc->S != S1) {
+        c->retire(lc->sp);
+        c->retire(lc->rootsum);
+        c->retire(lc->nd);
+        lc->nodes_cap = 0;
+        lc->S = S1;
+    }
+    if (c->spare_S != S1) {
+        c->retire(c->fc_spare);
+        c->spare_cap = 0;
+        c->spare_S = S1;
+    }
+    const size_t wlw = (size_t)c->p.value_len * c->p.w32;
+    const size_t nl = (size_t)2 * t->n_parents[t->L];
+    bool ok = c->reclaim_ensure(lc->sp, 0, 100 * S1 * 4, RECLAIM_ALL) &&
+              c->reclaim_ensure(lc->rootsum, 0, wlw * S1 * 4, RECLAIM_ALL);
+    if (ok && nl > c->spare_cap) {
+        const size_t cap = spare_capacity(nl, c->spare_cap, free_hbm(), S1);
+        // the spare may be a former slot that queued kernels still read:
+        // retire it, and free the retired buffers first
+        c->retire(c->fc_spare);
+        c->spare_cap = 0;
+        if (c->idle()) c->bury();
+        ok = c->reclaim_ensure(c->fc_spare, 0, cap * 5 * S1 * 4, RECLAIM_ALL);
+        if (ok) c->spare_cap = cap;
+    }
+    if (!ok) {  // not enough HBM for the cache: evaluate without it
+        lc->release();
+        return CacheUse();
+    }
+    if (!u.hit) lc->drop();  // refilled by this call
+    u.lc = lc;
+    u.cin = u.hit ? lc->nd.as<uint32_t>() : nullptr;
+    u.cout = c->fc_spare.as<uint32_t>();
+    return u;
+}
+
+// The work arena of a call: used as it is, or re-allocated (memplan.hpp
+// plan_arena).  *by_budget: the reports per chunk the call's budget allows.
+static int size_arena(mastic_ctx* c, size_t n, size_t per_report, bool cache_on, size_t* by_budget) {
+    const bool fits = arena_fits(c->m, n, per_report, c->work.bytes);
+    const uint64_t budget =
+        call_budget(c->m, n, per_report, fits, cache_on, (fits || c->m.budget) ? std::nullopt : free_hbm());
+    const ArenaPlan a = plan_arena(c->m, n, per_report, c->work.bytes, budget, cache_on);
+    *by_budget = a.by_budget;
+    if (a.action == ArenaPlan::TOO_SMALL)
+        return fail(c, MASTIC_ENOMEM, "work buffers of 64 reports exceed the memory budget");
+    if (a.action == ArenaPlan::USE) return 0;
+    c->rk.valid = false;  // the arena may be re-allocated (possibly at the same address)
+    if (!c->reclaim_ensure(c->work, a.arena, a.want, RECLAIM_BURIED))
+        return fail(c, MASTIC_ENOMEM, "out of device memory (work %zu bytes)", a.want);
+    return 0;
 }
 
 extern "C" int mastic_prep_init(mastic_ctx* c, mastic_reports* rep, const uint8_t* verify_key, size_t vk_len,
@@ -1146,189 +1267,27 @@ extern "C" int mastic_prep_init(mastic_ctx* c, mastic_reports* rep, const uint8_
     WorkLayout wl = work_layout(p, t);
     const size_t n = rep->n;
     Result& R = c->res[agg_id];
-    R.ready = false;
-    R.n = n;
-    R.stride = round_up(std::max<size_t>(n, 1), 64);
-    R.weight_check = t->weight_check;
-    R.n_prefixes = t->n_prefixes;
-    const size_t S = R.stride;
-    // a result buffer that must grow retires the old one to the graveyard
-    // (freed at the next idle point) instead of freeing it here: hipFree
-    // waits for the whole device, i.e. for the other aggregator's queued call
-    auto rgrow = [&](DevBuf& d, size_t want) {
-        if (want <= d.bytes && d.p) return true;
-        const size_t old = d.bytes;
-        if (d.p && d.own) c->graveyard.push_back(d.p);
-        d.p = nullptr;
-        d.bytes = 0;
-        d.own = true;
-        if (!c->inject_alloc_failure() && (d.ensure(std::max(want, old + old / 2)) || d.ensure(want))) return true;
-        // HBM is held by the work arena (sized to the budget when the results
-        // were smaller) and by retired buffers: once the queued work on all
-        // three streams is done, free both and retry; the arena is re-allocated
-        // below, within what is left (a 2M-report sweep's out shares reach 32 GB
-        // per aggregator)
-        if (!c->idle()) return false;
-        c->bury();
-        c->work.release();
-        c->rk.valid = false;
-        return d.ensure(want);
-    };
-    if (!rgrow(R.eval_proof, S * 8 * 4) || !rgrow(R.status, S * 4) ||
-        !rgrow(R.out, S * 4 * std::max<size_t>(1, (size_t)t->n_prefixes * (1 + p.output_len) * p.w32)) ||
-        !rgrow(R.verifier, S * 4 * (size_t)p.verifier_len * p.w32) || !rgrow(R.jr_part, S * 32) ||
-        !rgrow(R.jr_seed, S * 32))
-        return fail(c, MASTIC_ENOMEM, "out of device memory (results for %zu reports)", n);
-    HIPCHK(c, hipMemsetAsync(R.jr_part.p, 0, S * 32, c->stream));
-    HIPCHK(c, hipMemsetAsync(R.jr_seed.p, 0, S * 32, c->stream));
+    if ((rc = size_results(c, R, t, n))) return rc;
     if (n == 0) {
         R.ready = true;
         return 0;
     }
-    const size_t pad = (size_t)c->stride_pad;
-    // frontier cache (tiled binder buffers only): decide hit / miss and size
-    // the slot before the work buffer, so the HBM budget sees the cache
-    LevelCache* lc = nullptr;
-    bool hit = false;
-    const uint32_t* cin = nullptr;  // a hit's parents: this aggregator's node slot
-    uint32_t* cout = nullptr;       // the last level's nodes: the spare node slot
+    const size_t pad = (size_t)c->m.stride_pad;
     std::vector<uint8_t> lkey(1, (uint8_t)vk_len);
     lkey.insert(lkey.end(), verify_key, verify_key + vk_len);
     lkey.insert(lkey.end(), app_ctx, app_ctx + ctx_len);
-    if (c->frontier_cache && c->binder_tiled) {
-        lc = &c->lc[agg_id];
-        const size_t S1 = round_up(n, 64) + pad;
-        const int L = t->L;
-        hit = lc->valid && lc->rep_id == rep->id && lc->rep_gen == rep->generation() && lc->n == n && lc->S == S1 && lc->key == lkey &&
-              !t->weight_check && L == lc->L + 1 && (size_t)L <= lc->n_parents.size() &&
-              std::equal(t->n_parents.begin(), t->n_parents.begin() + L, lc->n_parents.begin()) &&
-              // level L-1's node paths fix every level above (each level's
-              // parents are the truncations of the next level's nodes), so
-              // they and the node counts decide that the trees agree there
-              lc->paths.size() == (t->off[L] - t->off[L - 1]) * 8 &&
-              std::equal(lc->paths.begin(), lc->paths.end(), t->child_path.begin() + t->off[L - 1] * 8);
-        auto retire = [&](DevBuf& b) {  // queued kernels may still read it
-            if (b.p && b.own) c->graveyard.push_back(b.p);
-            b.p = nullptr;
-            b.bytes = 0;
-        };
-        if (lc->S != S1) {
-            retire(lc->sp);
-            retire(lc->rootsum);
-            retire(lc->nd);
-            lc->nodes_cap = 0;
-            lc->S = S1;
-        }
-        if (c->spare_S != S1) {
-            retire(c->fc_spare);
-            c->spare_cap = 0;
-            c->spare_S = S1;
-        }
-        const size_t wlw = (size_t)p.value_len * p.w32;
-        const size_t nl = (size_t)2 * t->n_parents[L];
-        // an allocation that fails first reclaims what idle streams free: the
-        // retired slots and the work buffer (re-allocated below, to the budget)
-        auto alloc = [&](DevBuf& b, size_t bytes) -> bool {
-            if (!c->inject_alloc_failure() && b.ensure(bytes)) return true;
-            if (!c->idle()) return false;
-            c->bury();
-            c->work.release();
-            c->rk.valid = false;
-            return b.ensure(bytes);
-        };
-        bool ok = alloc(lc->sp, 100 * S1 * 4) && alloc(lc->rootsum, wlw * S1 * 4);
-        if (ok && nl > c->spare_cap) {
-            // grow geometrically (a sweep's frontier widens over several
-            // levels), and while HBM is plentiful straight to up to 4x the
-            // need within a fifth of the free memory: each large hipMalloc
-            // costs ~1 s per 50 GB, so a 1M-report sweep should grow its
-            // slots a couple of times, not at every level
-            size_t cap = std::max(nl, c->spare_cap + c->spare_cap / 4);
-            size_t freeb = 0, totalb = 0;
-            if (hipMemGetInfo(&freeb, &totalb) == hipSuccess) {
-                const size_t per_node = 5 * S1 * 4;
-                cap = std::max(cap, std::min(4 * nl, freeb / 5 / per_node));
-            }
-            // the spare may be a former slot that queued kernels still read:
-            // retire it, and free the retired buffers first
-            retire(c->fc_spare);
-            c->spare_cap = 0;
-            if (c->idle()) c->bury();
-            ok = alloc(c->fc_spare, cap * 5 * S1 * 4);
-            if (ok) c->spare_cap = cap;
-        }
-        if (!ok) {  // not enough HBM for the cache: evaluate without it
-            lc->release();
-            lc = nullptr;
-            hit = false;
-        } else {
-            cin = hit ? lc->nd.as<uint32_t>() : nullptr;
-            cout = c->fc_spare.as<uint32_t>();
-        }
-        if (!hit && lc) lc->drop();  // refilled by this call
-    } else {
-        c->lc[agg_id].drop();
-    }
-    // with the cache on, half of the free HBM: the other aggregator's slot may
-    // still grow at this level
-    const size_t per_report = wl.words * 4;
-    // (an arena that already holds the whole batch needs no budget: skip the
-    // free-memory query, ~tens of us per call)
-    const bool fits = !c->budget && c->work.bytes / per_report >= round_up(n, 64) + pad;
-    const uint64_t budget = fits ? (uint64_t)per_report * (round_up(n, 64) + pad)
-                            : (lc && !c->budget) ? default_budget(c) * 2 / 3 : default_budget(c);
-    // Plane rows are padded by stride_pad words: with a power-of-two row
-    // length every word of a report sits at the same address bits modulo a
-    // large power of two, and the 42-plane block loads of the binder sponges
-    // all land on the same memory channels.
-    size_t by_budget = (budget / per_report) / 64 * 64;
-    if (by_budget > pad + 64) by_budget -= pad;  // the padded rows count against the budget too
-    size_t chunk = std::min<size_t>(round_up(n, 64), by_budget);
-    // The work buffer is an arena kept across calls: a call uses all of its
-    // capacity (even past the budget: it is allocated already), and a new
-    // one is at least c->work_arena bytes (within the budget), so a level
-    // sweep whose trees grow from level to level does not re-allocate it at
-    // every level.
-    const size_t have = c->work.bytes / per_report;
-    // An arena that holds half the batch in chunks of >= 64k reports is used
-    // as it is (pipelined chunks of that size keep the GPU full and hide each
-    // other's sponge tails) rather than re-allocated for a single chunk.
-    const size_t need = std::min(chunk, round_up(n, 64)) + pad;
-    if (have >= need || (2 * have >= need && have >= pad + 2 * 65536)) {
-        chunk = std::min<size_t>(round_up(n, 64), (have - pad) / 64 * 64);
-    } else {
-        if (chunk < 64) return fail(c, MASTIC_ENOMEM, "work buffers of 64 reports exceed the memory budget");
-        const size_t want = per_report * (chunk + pad);
-        const size_t arena = std::max(want, std::min<size_t>(lc ? c->work_arena_fc : c->work_arena, budget));
-        c->rk.valid = false;  // the arena may be re-allocated (possibly at the same address)
-        if (!c->work.ensure(arena) && !c->work.ensure(want)) {
-            // retired buffers (cache slots, evicted trees) are freed once the stream is idle
-            if (c->graveyard.empty() || !c->idle())
-                return fail(c, MASTIC_ENOMEM, "out of device memory (work %zu bytes)", want);
-            c->bury();
-            if (!c->work.ensure(arena) && !c->work.ensure(want))
-                return fail(c, MASTIC_ENOMEM, "out of device memory (work %zu bytes)", want);
-        }
-        chunk = std::min<size_t>(round_up(n, 64), (c->work.bytes / per_report - pad) / 64 * 64);
-    }
-    if (c->budget) chunk = std::min(chunk, std::max<size_t>(by_budget, 64));  // an explicit budget caps chunks
-    // MASTIC_CHUNK_REPORTS caps a chunk below what fits, so a large batch runs
-    // as several pipelined chunks (the trailing sponges of one overlap the
-    // evaluation of the next) instead of one chunk with an exposed tail
-    const bool capped = c->chunk_max > 0 && round_up(c->chunk_max, 64) < chunk;
-    if (capped) chunk = round_up(c->chunk_max, 64);
-    // Several chunks: pipeline them through the two halves of the work arena
-    // (chunk k+1 evaluates in one half while chunk k's last sponges, finalize
-    // and copies run on the sponge stream over the other).
-    const size_t half_cap = c->work.bytes / 2 / per_report;  // reports (padding rows included) per half
-    const bool pipe = c->chunk_pipeline && n > chunk && chunk >= 128 && half_cap >= pad + 64;
-    if (pipe) chunk = std::min(capped ? chunk : chunk / 2, half_cap - pad) / 64 * 64;
-    const size_t half = c->work.bytes / 2 / 4 / 64 * 64;  // words: second half's offset
-    // the launch plans (schedule.hpp) of a full chunk and, if shorter, of the last one
-    const size_t n_full = std::min(chunk, n), n_last = n - (n - 1) / chunk * chunk;
-    ChunkPlan* plans[2] = {&c->plans[0], &c->plans[n_last != n_full]};
-    for (int i = 0; i <= (n_last != n_full); i++)
-        plan_chunk(c->k, p, *t, (int)(i ? n_last : n_full), hit, lc != nullptr, pipe, c->pfx_f[PFX_ONEHOT],
+    const CacheUse cu = cache_slots(c, agg_id, t, rep, lkey);
+    LevelCache* const lc = cu.lc;
+    const bool hit = cu.hit;
+    size_t by_budget = 0;
+    if ((rc = size_arena(c, n, wl.words * 4, lc != nullptr, &by_budget))) return rc;
+    // the chunks (memplan.hpp), and the launch plans (schedule.hpp) of a full chunk and, if shorter, of the last one
+    const ChunkSizes cs = plan_chunks(c->m, n, wl.words * 4, c->work.bytes, by_budget);
+    const size_t chunk = cs.chunk;
+    const bool pipe = cs.pipe;
+    ChunkPlan* plans[2] = {&c->plans[0], &c->plans[cs.n_last != cs.n_full]};
+    for (int i = 0; i <= (cs.n_last != cs.n_full); i++)
+        plan_chunk(c->k, p, *t, (int)(i ? cs.n_last : cs.n_full), hit, lc != nullptr, pipe, c->pfx_f[PFX_ONEHOT],
                    c->pfx_f[PFX_PAYLOAD], plans[i]);
     // sync events one chunk uses: pipelined chunks alternate between two disjoint ranges of them
     const size_t nsev = (size_t)std::max(plans[0]->n_sync, plans[1]->n_sync);
@@ -1340,12 +1299,12 @@ extern "C" int mastic_prep_init(mastic_ctx* c, mastic_reports* rep, const uint8_
         const int nn = (int)std::min(chunk, n - b), stride = (int)(round_up(nn, 64) + pad);
         const int h = pipe ? (int)(k & 1) : 0;
         if (pipe && k >= 2) HIPCHK(c, hipStreamWaitEvent(c->stream, half_free[h], 0));
-        uint32_t* W = c->work.as<uint32_t>() + h * half;
+        uint32_t* W = c->work.as<uint32_t>() + h * cs.half;
         // pipelined chunks alternate between two sponge streams: a chunk's
         // sponges must not queue behind the previous chunk's trailing ones
         hipStream_t ss = (pipe && h) ? c->stream3 : c->stream2, tail = pipe ? ss : c->stream;
-        Chunk ck{c, rep, t, wl, *plans[b + chunk >= n], agg_id, nn, stride, b, W, ss, tail, lc, hit, cin, cout, evi,
-                 h * nsev};
+        Chunk ck{c, rep, t, wl, *plans[b + chunk >= n], agg_id, nn, stride, b, W, ss, tail, lc, hit, cu.cin, cu.cout,
+                 evi, h * nsev};
         rc = p.field == 64 ? ck.run<F64>() : ck.run<F128>();
         if (rc) {
             if (lc) lc->drop();
@@ -1368,15 +1327,7 @@ extern "C" int mastic_prep_init(mastic_ctx* c, mastic_reports* rep, const uint8_
         std::swap(lc->nd.p, c->fc_spare.p);
         std::swap(lc->nd.bytes, c->fc_spare.bytes);
         std::swap(lc->nodes_cap, c->spare_cap);
-        lc->valid = true;
-        lc->rep_id = rep->id;
-        lc->rep_gen = rep->generation();
-        lc->n = n;
-        lc->key = lkey;
-        lc->L = t->L;
-        lc->n_parents.assign(t->n_parents.begin(), t->n_parents.begin() + t->L + 1);
-        lc->paths.assign(t->child_path.begin() + t->off[t->L] * 8,
-                         t->child_path.begin() + (t->off[t->L] + 2 * t->n_parents[t->L]) * 8);
+        frontier_commit(*lc, *t, rep->id, rep->generation(), n, lkey);
     }
     c->last_hit = hit;
     HIPCHK(c, hipEventRecord(t1, c->stream));
@@ -2535,9 +2486,9 @@ extern "C" int mastic_ctx_create(const mastic_params* up, mastic_ctx** out) {
         const char* pw = getenv("MASTIC_PROOF_WAVES");
         if (pw) c->k.proof_waves = std::max(1, std::min(15, atoi(pw)));
         const char* spd = getenv("MASTIC_STRIDE_PAD");
-        if (spd) c->stride_pad = std::max(0, std::min(1 << 20, atoi(spd))) / 64 * 64;
+        if (spd) c->m.stride_pad = std::max(0, std::min(1 << 20, atoi(spd))) / 64 * 64;
         const char* wa = getenv("MASTIC_WORK_ARENA_GB");
-        if (wa) c->work_arena = c->work_arena_fc = (size_t)std::max(0, atoi(wa)) << 30;
+        if (wa) c->m.work_arena = c->m.work_arena_fc = (size_t)std::max(0, atoi(wa)) << 30;
         const char* bt = getenv("MASTIC_BINDER_TILED");
         if (bt) c->binder_tiled = bt[0] != '0';
         const char* at = getenv("MASTIC_ABSORB_THREADS");
@@ -2555,7 +2506,7 @@ extern "C" int mastic_ctx_create(const mastic_params* up, mastic_ctx** out) {
         const char* pw2 = getenv("MASTIC_PAR_WAVES");
         if (pw2) c->k.par_waves = std::max(1, std::min(EVAL_WAVES, atoi(pw2)));
         const char* cp = getenv("MASTIC_CHUNK_PIPELINE");
-        if (cp) c->chunk_pipeline = cp[0] != '0';
+        if (cp) c->m.chunk_pipeline = cp[0] != '0';
         const char* hpw = getenv("MASTIC_HIT_PROOF_WAVES");
         if (hpw) c->k.hit_proof_waves = std::max(0, std::min(15, atoi(hpw)));
         const char* fp = getenv("MASTIC_FUSE_PROOFS");
@@ -2563,7 +2514,7 @@ extern "C" int mastic_ctx_create(const mastic_params* up, mastic_ctx** out) {
         const char* fa = getenv("MASTIC_FC_ALL");
         if (fa) c->k.fc_all = fa[0] == '1';
         const char* cr = getenv("MASTIC_CHUNK_REPORTS");
-        if (cr) c->chunk_max = (size_t)std::max(0, atoi(cr));
+        if (cr) c->m.chunk_max = (size_t)std::max(0, atoi(cr));
         const char* spl = getenv("MASTIC_SPLIT_SPONGES");
         if (spl) c->k.split_sponges = spl[0] == '1' ? 1 : 0;
         const char* flm = getenv("MASTIC_FUSE_LAST_MISS");
@@ -2633,16 +2584,10 @@ extern "C" int mastic_set_frontier_cache(mastic_ctx* c, int on, int* last_hit) {
             // queued kernels may still read the cache slots: retire them (freed
             // at the next idle point of the ctx's streams), no synchronisation
             for (auto& x : c->lc) {
-                for (DevBuf* b : {&x.sp, &x.rootsum, &x.nd}) {
-                    if (b->p && b->own) c->graveyard.push_back(b->p);
-                    b->p = nullptr;
-                    b->bytes = 0;
-                }
+                for (DevBuf* b : {&x.sp, &x.rootsum, &x.nd}) c->retire(*b);
                 x.release();
             }
-            if (c->fc_spare.p && c->fc_spare.own) c->graveyard.push_back(c->fc_spare.p);
-            c->fc_spare.p = nullptr;
-            c->fc_spare.bytes = 0;
+            c->retire(c->fc_spare);
             c->spare_cap = 0;
             c->spare_S = 0;
         }
@@ -2683,7 +2628,7 @@ extern "C" int mastic_abi_version(void) { return MASTIC_ABI_VERSION; }
 
 extern "C" int mastic_set_memory_budget(mastic_ctx* c, uint64_t bytes) {
     if (!c) return MASTIC_EINVAL;
-    c->budget = bytes;
+    c->m.budget = bytes;
     return 0;
 }
 

@@ -2,8 +2,9 @@
 
 A result buffer or frontier-cache slot that cannot be allocated makes
 prep_init wait for everything queued on the ctx's three streams, free the
-retired buffers and the work arena, and retry (mastic_hip.hip ``rgrow`` and
-the cache ``alloc``).  At full scale only C3's 2M-report sweep reaches it, so
+retired buffers and the work arena, and retry (mastic_hip.hip
+``mastic_ctx::reclaim_ensure`` with ``RECLAIM_ALL``, from ``size_results`` and
+``cache_slots``).  At full scale only C3's 2M-report sweep reaches it, so
 the result-preserving ``fail_allocs`` test hook (``mastic_set_test_hooks``)
 forces those allocations to fail: the outputs must be bit-identical to an
 unconstrained context, and every injected failure must have been consumed

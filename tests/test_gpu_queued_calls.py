@@ -191,3 +191,43 @@ def test_hit_timing_with_busy_sponge_stream(mastic_amd):
         assert t[-1] > 0
     finally:
         m.set_frontier_cache(False)
+
+
+def test_cache_switched_off_beside_queued_hit(mastic_amd):
+    """set_frontier_cache(False) while aggregator 0's hit is still queued: the
+    cache slots that its kernels read and write are retired, not freed
+    (mastic_ctx::retire).  Aggregator 1's call at the same level then runs
+    without the cache over the shared work arena, and so does a further call of
+    aggregator 0.  Every result equals a cache-off context's, bit for bit."""
+    rng = random.Random(96)
+    m_off = mastic_amd.MasticCount(9)
+    m_on = mastic_amd.MasticCount(9)
+    n = 180
+    (alphas, weights, nonces, rands) = _reports(m_off, rng, n, 10)
+    (pub, in0, in1) = m_off.shard_batch(CTX, alphas, weights, nonces, rands)
+    vk = bytes(rng.getrandbits(8) for _ in range(32))
+    dev_off = m_off.reports_upload(nonces, pub, in0, in1)
+    dev_on = m_on.reports_upload(nonces, pub, in0, in1)
+    # levels 2 and 3 with every prefix that occurs: the second tree extends the first by one level
+    (ap0, ap1) = [(lv, tuple(sorted({a[:lv + 1] for a in alphas})), False) for lv in (2, 3)]
+    (want, _) = _pair(m_off, dev_off, (vk, vk), (ap1, ap1), (0, 1))
+
+    def same(got, a):
+        assert got[0] == want[a][0] and got[2] == want[a][2], a
+        assert (got[3] == want[a][3]).all(), a
+
+    m_on.set_frontier_cache(True)
+    try:
+        for a in (0, 1):
+            m_on.prep_init_device(dev_on, vk, CTX, a, ap0)
+        m_on.prep_init_device(dev_on, vk, CTX, 0, ap1)
+        assert m_on.last_prep_was_cached()
+    finally:
+        m_on.set_frontier_cache(False)
+    m_on.prep_init_device(dev_on, vk, CTX, 1, ap1)
+    assert not m_on.last_prep_was_cached()
+    for a in (1, 0):
+        same(m_on.prep_result(dev_on, a, ap1, want_out_shares=True), a)
+    m_on.prep_init_device(dev_on, vk, CTX, 0, ap1)
+    assert not m_on.last_prep_was_cached()
+    same(m_on.prep_result(dev_on, 0, ap1, want_out_shares=True), 0)
