@@ -630,6 +630,23 @@ struct AesArgs {
     uint32_t* wp_buf;
     int recompute_wp;
     int in_stride;  // plane stride of cs_in (the cache's, on a hit; else the work buffer's)
+    // Node formats (FC only; mastic_set_frontier_cache_nodes).  A slot holds seeds-format nodes (the
+    // 5 words above) or payloads-format nodes: [next seed 4][ctrl][payload, VALUE_LEN * w32 words],
+    // the next seed being block 0 of the node's convert stream and the payload as emit corrected it.
+    // The slot a hit reads and the slot the call writes may differ in format, so the two switches
+    // are independent (both live in the PAY instantiation, launched when either is > 5).
+    // in_nw: words per node of cs_in (5: the work buffer's child seeds, or a seeds-format slot, then
+    // recompute_wp = 1 on a hit; > 5: a payloads-format slot, whose parents need no recompute and
+    // whose payload the children read from the slot, plane stride in_stride).
+    // out_nw: words per node of cache_out (> 5: emit also stores both children's corrected elements
+    // into their nodes and the header takes the next seeds).  That is safe because a launch that
+    // writes the cache is a call's last level, which emits out shares and is therefore never split
+    // into block-range items (every element of a node comes from the one item that owns the parent),
+    // and because it is never cut into parent ranges (schedule.hpp plan_chunk segments a last level
+    // only without the cache; the host offsets cache_out by a range's first parent as it does
+    // cs_out), so cache_out is indexed by parent.
+    int in_nw;
+    int out_nw;
     // frontier-cache hit (FC only): the AES waves also compute THIS level's
     // node proofs right after each parent's payloads (no k_node_proof launch)
     int fuse_proofs;
@@ -822,9 +839,13 @@ MH_D void parent_payload(const AesPerm& TL, const RkLds& rkc, const uint32_t cv[
 // never with FC); a separate instantiation so the other levels' kernels carry
 // none of its bookkeeping (in the plain kernel it quadrupled the SGPR spills).
 // WIDE: the 104-VGPR budget above; the proof waves run the fused-theta
-// permutation (never with FC).  One body, two kernels (k_eval_aes and
-// k_eval_aes_wide below) that differ in their register attributes only.
-template <class F, bool GEN, bool FC, bool SPLIT, bool WIDE>
+// permutation (never with FC).  PAY (only with FC): the payloads node format
+// of the frontier cache (AesArgs::in_nw / out_nw) is compiled in, for a launch
+// whose input or output slot has it; the seeds-only FC kernel carries none of
+// it (in one kernel the two formats cost it 80 more spilled SGPRs).  One body,
+// two kernels (k_eval_aes and k_eval_aes_wide below) that differ in their
+// register attributes only.
+template <class F, bool GEN, bool FC, bool SPLIT, bool WIDE, bool PAY = false>
 MH_D void eval_aes_body(const McParams& p, const Planes& pl, const AesArgs& a) {
     typedef typename F::E E;
     // dynamic LDS (EVAL_LDS_BYTES): with a static size the compiler derives
@@ -842,6 +863,8 @@ MH_D void eval_aes_body(const McParams& p, const Planes& pl, const AesArgs& a) {
 
     const int S = pl.stride;
     const int S_in = FC ? a.in_stride : S;  // cs_in / fr_w_in
+    const int NW_in = (FC && PAY) ? a.in_nw : 5;     // words per node of cs_in (AesArgs::in_nw)
+    const int NW_out = (FC && PAY) ? a.out_nw : 5;  // ... of cache_out (AesArgs::out_nw)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = blockIdx.x * 64 + lane;
@@ -1029,9 +1052,10 @@ MH_D void eval_aes_body(const McParams& p, const Planes& pl, const AesArgs& a) {
             pctrl = a.agg_id;
         } else {
             const int pn = a.parent_node[pi];
+            const size_t n0 = (size_t)pn * NW_in;  // either node format starts with a seed and the control bit
 #pragma unroll
-            for (int i = 0; i < 4; i++) ps[i] = pld(a.cs_in + ((size_t)pn * 5 + i) * S_in, lb);
-            pctrl = pld(a.cs_in + ((size_t)pn * 5 + 4) * S_in, lb);
+            for (int i = 0; i < 4; i++) ps[i] = pld(a.cs_in + (n0 + i) * S_in, lb);
+            pctrl = pld(a.cs_in + (n0 + 4) * S_in, lb);
         }
     };
     uint32_t nps[4], npctrl;
@@ -1124,13 +1148,15 @@ MH_D void eval_aes_body(const McParams& p, const Planes& pl, const AesArgs& a) {
 #endif
         if constexpr (FC) {
             if (a.cache_out) {
-                // the last level's children as frontier-cache nodes: convert seed, control bit
+                // the last level's children as frontier-cache nodes: convert seed (payloads
+                // format: next seed; emit below adds the payload), control bit
                 const int CS = a.cache_stride;
-                const size_t n0 = (size_t)(2 * pi) * 5, n1 = n0 + 5;
+                const bool pay = NW_out > 5;
+                const size_t n0 = (size_t)(2 * pi) * NW_out, n1 = n0 + NW_out;
 #pragma unroll
                 for (int i = 0; i < 4; i++) {
-                    pst(a.cache_out + (n0 + i) * CS, lb, cs0[i]);
-                    pst(a.cache_out + (n1 + i) * CS, lb, cs1[i]);
+                    pst(a.cache_out + (n0 + i) * CS, lb, pay ? ns0[i] : cs0[i]);
+                    pst(a.cache_out + (n1 + i) * CS, lb, pay ? ns1[i] : cs1[i]);
                 }
                 pst(a.cache_out + (n0 + 4) * CS, lb, tc0);
                 pst(a.cache_out + (n1 + 4) * CS, lb, tc1);
@@ -1160,9 +1186,25 @@ MH_D void eval_aes_body(const McParams& p, const Planes& pl, const AesArgs& a) {
 #else
         constexpr bool x_fr = true, x_diff = true;
 #endif
+        // payloads-format cache nodes of the two children (FC, AesArgs::out_nw > 5): their payload planes
+        uint32_t* cpay0 = nullptr;
+        uint32_t* cpay1 = nullptr;
+        if constexpr (FC && PAY) {
+            if (a.cache_out && NW_out > 5) {
+                cpay0 = a.cache_out + ((size_t)(2 * pi) * NW_out + 5) * a.cache_stride;
+                cpay1 = cpay0 + (size_t)NW_out * a.cache_stride;
+            }
+        }
         auto emit = [&](int e, E x0, E x1, E cw, E wp) {
             if (tc0) x0 = F::add(x0, cw);
             if (tc1) x1 = F::add(x1, cw);
+            if constexpr (FC && PAY) {
+                // the same coalesced plane stores as fr_w_out's (the last level makes none of those)
+                if (cpay0) {
+                    pl_store<F>(cpay0, e, a.cache_stride, r, x0);
+                    pl_store<F>(cpay1, e, a.cache_stride, r, x1);
+                }
+            }
             if (x_fr && ce0 >= 0) pl_store<F>(a.fr_w_out, ce0 * vl + e, S, r, x0);
             if (x_fr && ce1 >= 0) pl_store<F>(a.fr_w_out, ce1 * vl + e, S, r, x1);
             if (GEN && l == 0) {
@@ -1199,14 +1241,23 @@ MH_D void eval_aes_body(const McParams& p, const Planes& pl, const AesArgs& a) {
         };
         auto load_cw = [&](int e) { return pl_load<F>(wcw, e, S, r); };
         const uint32_t* wpb = a.fr_w_in;
-        if constexpr (FC) wpb = a.recompute_wp ? a.wp_buf : a.fr_w_in;
+        int wp_S = S, wp_e0 = pi * vl;  // plane stride and first element of this parent's payload in wpb
+        if constexpr (FC) {
+            wpb = a.recompute_wp ? a.wp_buf : a.fr_w_in;
+            if (PAY && NW_in > 5) {
+                // a hit on a payloads-format slot: the parent's payload straight from its node
+                wpb = a.cs_in + ((size_t)a.parent_node[pi] * NW_in + 5) * S_in;
+                wp_S = S_in;
+                wp_e0 = 0;
+            }
+        }
         // level 0: the root's "parent payload" planes are zeroed by the host
         // (no branch, no zero-initialised registers in the block loop)
 #ifdef MASTIC_EXPERIMENT_KNOBS
         const bool x_wp = !(a.dbg_skip & 16);
-        auto load_wp = [&](int e) { return x_wp ? pl_load<F>(wpb, pi * vl + e, S, r) : F::from_u64((uint64_t)e); };
+        auto load_wp = [&](int e) { return x_wp ? pl_load<F>(wpb, wp_e0 + e, wp_S, r) : F::from_u64((uint64_t)e); };
 #else
-        auto load_wp = [&](int e) { return pl_load<F>(wpb, pi * vl + e, S, r); };
+        auto load_wp = [&](int e) { return pl_load<F>(wpb, wp_e0 + e, wp_S, r); };
 #endif
         int e_fast = e_lo;  // elements completed by the fast path
 #if MASTIC_EMIT_WAIT
@@ -1324,10 +1375,10 @@ aes_done:
     }
 }
 
-template <class F, bool GEN, bool FC, bool SPLIT = false>
+template <class F, bool GEN, bool FC, bool SPLIT = false, bool PAY = false>
 __global__ __launch_bounds__(64 * EVAL_WAVES) EVAL_VGPR_ATTR
 void k_eval_aes(McParams p, Planes pl, AesArgs a) {
-    eval_aes_body<F, GEN, FC, SPLIT, false>(p, pl, a);
+    eval_aes_body<F, GEN, FC, SPLIT, false, PAY>(p, pl, a);
 }
 template <class F, bool GEN, bool SPLIT = false>
 __global__ __launch_bounds__(64 * EVAL_WAVES) EVAL_WIDE_ATTR

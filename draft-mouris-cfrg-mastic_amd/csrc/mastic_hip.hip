@@ -131,8 +131,12 @@ struct Result {
 // after the cached call's levels (the binder messages are BFS-ordered, so the
 // cached message is a prefix of the next one), every node of the last level as
 // its convert seed and control bit (5 words: a hit recomputes a parent's seed
-// and payload from its convert stream), and the root sum; a call whose tree
-// extends the cached one by one level evaluates and absorbs only that level.
+// and payload from its convert stream) or, where the call that wrote the slot
+// chose the payloads format (mastic_set_frontier_cache_nodes, memplan.hpp
+// choose_node_words), as its next seed, control bit and corrected payload
+// (5 + VALUE_LEN * w32 words: a hit recomputes nothing), and the root sum; a
+// call whose tree extends the cached one by one level evaluates and absorbs
+// only that level.
 // Planes of all n reports (stride S, independent of the HBM-budget chunks a
 // call runs in, so a sweep's chunking may change from level to level).  The
 // last level kernel writes its children straight into a spare node slot
@@ -142,14 +146,14 @@ struct Result {
 // The host metadata (what was cached, the hit test) is memplan.hpp FrontierMeta.
 struct LevelCache : FrontierMeta {
     DevBuf sp, rootsum;    // both binder sponges (2 x 50 planes); root sum (wl planes)
-    DevBuf nd;             // last level's nodes [node][5]: convert seed, control bit
-    size_t nodes_cap = 0;  // nodes nd can hold
+    DevBuf nd;             // last level's nodes [node][node_words] (FrontierMeta: the format of the call that wrote them)
+    size_t nd_words = 0;   // words per plane row nd can hold (nodes x words per node, either format)
     void release() {
         drop();
         sp.release();
         rootsum.release();
         nd.release();
-        nodes_cap = 0;
+        nd_words = 0;
         S = 0;
     }
 };
@@ -244,7 +248,9 @@ struct mastic_ctx {
     bool last_hit = false;        // the last prep_init evaluated only its last level
     LevelCache lc[2];
     DevBuf fc_spare;          // the frontier cache's spare node slot (LevelCache::nd layout)
-    size_t spare_cap = 0;     // nodes it can hold
+    size_t spare_words = 0;   // words per plane row it can hold
+    int fc_nodes = FC_NODES_SEEDS;         // the node format cache-on calls write (mastic_set_frontier_cache_nodes)
+    int last_nodes_in = -1, last_nodes_out = -1;  // the last prep_init: format its hit read / it wrote (-1: none)
     size_t spare_S = 0;       // its plane stride
     std::vector<void*> graveyard;  // replaced cache slots, freed once the streams are idle
     // The AES key schedules in the work arena (k_setup): the reports, ctx and
@@ -680,6 +686,7 @@ template <class F>
 static LevelKernel level_kernel(int variant) {
     switch (variant) {
     case LV_GEN | LV_FC: return k_eval_aes<F, true, true>;
+    case LV_FC_PAY: return k_eval_aes<F, true, true, false, true>;
     case 0: return k_eval_aes<F, false, false>;
     case LV_GEN: return k_eval_aes<F, true, false>;
     case LV_SPLIT: return k_eval_aes<F, false, false, true>;
@@ -716,6 +723,7 @@ struct Chunk {
     bool hit;
     const uint32_t* cin;
     uint32_t* cout;
+    int in_nw, out_nw;  // words per node of cin / cout (CacheUse)
     size_t& evi;
     size_t sev;
     Planes pl;
@@ -953,10 +961,13 @@ struct Chunk {
         // frontier cache: stage this level's convert seeds (last level); on a
         // hit recompute the parents' payloads from the cached ones into the
         // (otherwise unused) parent-payload planes
-        a.cache_out = (lc && l == t->L) ? cout + base : nullptr;
+        a.cache_out = (lc && l == t->L) ? cout + base + 2 * p0 * (size_t)out_nw * lc->S : nullptr;
         a.cache_stride = lc ? (int)lc->S : 0;
         a.wp_buf = plane(wl.fr_w[(l + 1) & 1]);
-        a.recompute_wp = hit ? 1 : 0;
+        // a payloads-format slot holds the parents' next seeds and payloads: nothing to recompute
+        a.in_nw = hit ? in_nw : SEED_NODE_WORDS;
+        a.out_nw = out_nw;
+        a.recompute_wp = (hit && in_nw == SEED_NODE_WORDS) ? 1 : 0;
         a.fuse_proofs = v.fuse_proofs;
         a.cur_path_bytes = (l + 1 + 7) / 8;
         a.cur_child_path = t->d_path + (t->off[l] + 2 * p0) * 8;
@@ -981,7 +992,9 @@ struct Chunk {
         a.bin_rstride = bin_rstride;
         a.np = (const PrefixState*)c->pfx.p + PFX_NODE;
         a.np_f = c->pfx_f[PFX_NODE];
-        hipLaunchKernelGGL(level_kernel<F>(v.variant), dim3(groups(), v.gy), dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES,
+        // the FC kernel that knows the payloads node format, where a slot of this launch has it
+        const bool pay = (v.variant & LV_FC) && (a.in_nw > SEED_NODE_WORDS || (a.cache_out && a.out_nw > SEED_NODE_WORDS));
+        hipLaunchKernelGGL(level_kernel<F>(pay ? LV_FC_PAY : v.variant), dim3(groups(), v.gy), dim3(64 * EVAL_WAVES), EVAL_LDS_BYTES,
                            c->stream, c->p, pl, a);
     }
 
@@ -1179,6 +1192,8 @@ struct CacheUse {
     bool hit = false;               // it evaluates only its last level
     const uint32_t* cin = nullptr;  // a hit's parents: this aggregator's node slot
     uint32_t* cout = nullptr;       // the last level's nodes: the spare node slot
+    int in_nw = SEED_NODE_WORDS;    // words per node of cin (the format of the call that wrote it)
+    int out_nw = SEED_NODE_WORDS;   // words per node this call writes into cout
 };
 
 // Frontier cache (tiled binder buffers only): decide hit / miss and size the
@@ -1197,27 +1212,50 @@ static CacheUse cache_slots(mastic_ctx* c, int agg_id, const Tree* t, const mast
         c->retire(lc->sp);
         c->retire(lc->rootsum);
         c->retire(lc->nd);
-        lc->nodes_cap = 0;
+        lc->nd_words = 0;
         lc->S = S1;
     }
     if (c->spare_S != S1) {
         c->retire(c->fc_spare);
-        c->spare_cap = 0;
+        c->spare_words = 0;
         c->spare_S = S1;
     }
     const size_t wlw = (size_t)c->p.value_len * c->p.w32;
     const size_t nl = (size_t)2 * t->n_parents[t->L];
     bool ok = c->reclaim_ensure(lc->sp, 0, 100 * S1 * 4, RECLAIM_ALL) &&
               c->reclaim_ensure(lc->rootsum, 0, wlw * S1 * 4, RECLAIM_ALL);
-    if (ok && nl > c->spare_cap) {
-        const size_t cap = spare_capacity(nl, c->spare_cap, free_hbm(), S1);
+    // The format this call writes (memplan.hpp choose_node_words); auto asks for the free HBM.
+    std::optional<size_t> free_bytes;
+    bool queried = false;
+    auto free_now = [&] {
+        if (!queried) free_bytes = free_hbm();
+        queried = true;
+        return free_bytes;
+    };
+    const size_t held = c->lc[0].nd.bytes + c->lc[1].nd.bytes + c->fc_spare.bytes;
+    const bool by_rule = c->fc_nodes == FC_NODES_AUTO;
+    size_t nw = (size_t)choose_node_words(c->fc_nodes, nl, wlw, S1, by_rule ? free_now() : std::nullopt, held);
+    if (ok && !slot_holds(c->spare_words, nl, nw)) {
         // the spare may be a former slot that queued kernels still read:
         // retire it, and free the retired buffers first
+        const size_t old_words = c->spare_words;
         c->retire(c->fc_spare);
-        c->spare_cap = 0;
+        c->spare_words = 0;
         if (c->idle()) c->bury();
-        ok = c->reclaim_ensure(c->fc_spare, 0, cap * 5 * S1 * 4, RECLAIM_ALL);
-        if (ok) c->spare_cap = cap;
+        if (nw > SEED_NODE_WORDS) {
+            // the wide format is an optimisation: one attempt, no draining of the
+            // streams or release of the work arena for it; else seeds width
+            const size_t words = spare_slot_words(nl, nw, old_words, free_now(), S1, by_rule, held);
+            if (!c->inject_alloc_failure() && c->fc_spare.ensure(words * S1 * 4))
+                c->spare_words = words;
+            else
+                nw = SEED_NODE_WORDS;
+        }
+        if (nw == SEED_NODE_WORDS) {
+            const size_t words = spare_slot_words(nl, nw, old_words, free_now(), S1);
+            ok = c->reclaim_ensure(c->fc_spare, 0, words * S1 * 4, RECLAIM_ALL);
+            if (ok) c->spare_words = words;
+        }
     }
     if (!ok) {  // not enough HBM for the cache: evaluate without it
         lc->release();
@@ -1227,6 +1265,8 @@ static CacheUse cache_slots(mastic_ctx* c, int agg_id, const Tree* t, const mast
     u.lc = lc;
     u.cin = u.hit ? lc->nd.as<uint32_t>() : nullptr;
     u.cout = c->fc_spare.as<uint32_t>();
+    u.in_nw = u.hit ? lc->node_words : SEED_NODE_WORDS;
+    u.out_nw = (int)nw;
     return u;
 }
 
@@ -1304,7 +1344,7 @@ extern "C" int mastic_prep_init(mastic_ctx* c, mastic_reports* rep, const uint8_
         // sponges must not queue behind the previous chunk's trailing ones
         hipStream_t ss = (pipe && h) ? c->stream3 : c->stream2, tail = pipe ? ss : c->stream;
         Chunk ck{c, rep, t, wl, *plans[b + chunk >= n], agg_id, nn, stride, b, W, ss, tail, lc, hit, cu.cin, cu.cout,
-                 evi, h * nsev};
+                 cu.in_nw, cu.out_nw, evi, h * nsev};
         rc = p.field == 64 ? ck.run<F64>() : ck.run<F128>();
         if (rc) {
             if (lc) lc->drop();
@@ -1326,10 +1366,13 @@ extern "C" int mastic_prep_init(mastic_ctx* c, mastic_reports* rep, const uint8_
         // spare, overwritten only by later calls' kernels (stream order)
         std::swap(lc->nd.p, c->fc_spare.p);
         std::swap(lc->nd.bytes, c->fc_spare.bytes);
-        std::swap(lc->nodes_cap, c->spare_cap);
-        frontier_commit(*lc, *t, rep->id, rep->generation(), n, lkey);
+        std::swap(lc->nd_words, c->spare_words);
+        frontier_commit(*lc, *t, rep->id, rep->generation(), n, lkey, cu.out_nw);
     }
     c->last_hit = hit;
+    auto fmt = [](int nw) { return nw > SEED_NODE_WORDS ? FC_NODES_PAYLOADS : FC_NODES_SEEDS; };
+    c->last_nodes_in = hit ? fmt(cu.in_nw) : -1;
+    c->last_nodes_out = lc ? fmt(cu.out_nw) : -1;
     HIPCHK(c, hipEventRecord(t1, c->stream));
     c->tm[c->tcur].n_eval = -(int)evi;  // timing pending (resolved by mastic_last_timing)
     R.ready = true;
@@ -2548,6 +2591,8 @@ extern "C" int mastic_ctx_create(const mastic_params* up, mastic_ctx** out) {
     for (int v : LEVEL_VARIANTS)
         attrs = attrs && lds((const void*)level_kernel<F64>(v), EVAL_LDS_BYTES) &&
                 lds((const void*)level_kernel<F128>(v), EVAL_LDS_BYTES);
+    attrs = attrs && lds((const void*)level_kernel<F64>(LV_FC_PAY), EVAL_LDS_BYTES) &&
+            lds((const void*)level_kernel<F128>(LV_FC_PAY), EVAL_LDS_BYTES);
     // the binder sponges are the latency-critical chain: their stream gets the
     // highest priority so their workgroups are dispatched first
     int prio_lo = 0, prio_hi = 0;
@@ -2588,12 +2633,22 @@ extern "C" int mastic_set_frontier_cache(mastic_ctx* c, int on, int* last_hit) {
                 x.release();
             }
             c->retire(c->fc_spare);
-            c->spare_cap = 0;
+            c->spare_words = 0;
             c->spare_S = 0;
         }
     }
     if (last_hit) *last_hit = c->last_hit ? 1 : 0;
     return 0;
+}
+
+extern "C" int mastic_set_frontier_cache_nodes(mastic_ctx* c, int mode, int* last_in, int* last_out) {
+    if (!c || mode > FC_NODES_AUTO) return MASTIC_EINVAL;
+    const int prev = c->fc_nodes;
+    // the slots keep their formats (a hit reads either), so the cache stays as it is
+    if (mode >= 0) c->fc_nodes = mode;
+    if (last_in) *last_in = c->last_nodes_in;
+    if (last_out) *last_out = c->last_nodes_out;
+    return prev;
 }
 
 extern "C" int mastic_set_test_hooks(mastic_ctx* c, int force_slow_blk, int fail_allocs) {

@@ -40,11 +40,23 @@ struct FrontierMeta {
     int L = -1;                   // level of the cached call
     std::vector<int> n_parents;   // per level 0..L
     std::vector<uint32_t> paths;  // child paths of level L (8 words per node)
+    int node_words = 5;           // words per node of the aggregator's slot (the format of the call that wrote it)
     void drop() { valid = false; }
 };
 
+// The two formats of a cached node (mastic_set_frontier_cache_nodes).  seeds:
+// [convert seed 4][ctrl], 5 words; a hit recomputes the parent's next seed and
+// payload from its convert stream.  payloads: [next seed 4][ctrl][payload], the
+// payload as the level kernel's emit corrected it, wlw = VALUE_LEN * w32 words.
+// A slot's format is that of the call that wrote it (FrontierMeta::node_words);
+// a hit reads either, whatever it writes itself.
+enum NodeMode { FC_NODES_SEEDS = 0, FC_NODES_PAYLOADS = 1, FC_NODES_AUTO = 2 };
+constexpr int SEED_NODE_WORDS = 5;
+inline int payload_node_words(size_t wlw) { return SEED_NODE_WORDS + (int)wlw; }
+
 // A call over tree t extends the cached call by exactly one level, over the
 // same batch contents, plane stride S1 and key: it evaluates only level L.
+// The slot's node format (lc.node_words) is not compared: either format hits.
 inline bool frontier_hit(const FrontierMeta& lc, const TreeShape& t, uint64_t rep_id, uint64_t rep_gen, size_t n,
                          size_t S1, const std::vector<uint8_t>& key) {
     const int L = t.L;
@@ -60,8 +72,9 @@ inline bool frontier_hit(const FrontierMeta& lc, const TreeShape& t, uint64_t re
 
 // The call over tree t has filled the cache (S was set when its slots were sized).
 inline void frontier_commit(FrontierMeta& lc, const TreeShape& t, uint64_t rep_id, uint64_t rep_gen, size_t n,
-                            const std::vector<uint8_t>& key) {
+                            const std::vector<uint8_t>& key, int node_words = SEED_NODE_WORDS) {
     lc.valid = true;
+    lc.node_words = node_words;
     lc.rep_id = rep_id;
     lc.rep_gen = rep_gen;
     lc.n = n;
@@ -78,13 +91,56 @@ inline void frontier_commit(FrontierMeta& lc, const TreeShape& t, uint64_t rep_i
 // to 4x the need within a fifth of the free memory: each large hipMalloc costs
 // ~1 s per 50 GB, so a 1M-report sweep should grow its slots a couple of
 // times, not at every level.
-inline size_t spare_capacity(size_t nl, size_t spare_cap, std::optional<size_t> free_bytes, size_t S1) {
+// node_words: the node format the slot is sized for.
+inline size_t spare_capacity(size_t nl, size_t spare_cap, std::optional<size_t> free_bytes, size_t S1,
+                             size_t node_words = SEED_NODE_WORDS) {
     size_t cap = std::max(nl, spare_cap + spare_cap / 4);
     if (free_bytes) {
-        const size_t per_node = 5 * S1 * 4;
+        const size_t per_node = node_words * S1 * 4;
         cap = std::max(cap, std::min(4 * nl, *free_bytes / 5 / per_node));
     }
     return cap;
+}
+
+// Slots are sized and tracked in words per plane row, not in nodes: a slot of
+// slot_words holds nl nodes of node_words each if they fit, whichever format
+// it was allocated for (a payload-width slot of c nodes holds c * NW / 5
+// seeds-format nodes of a later, wider level without growing).
+inline bool slot_holds(size_t slot_words, size_t nl, size_t node_words) { return nl * node_words <= slot_words; }
+
+// The cache's share of the HBM: with the cache on, call_budget plans the work
+// arena with half of the free memory where default_budget takes three
+// quarters, so a quarter is the cache's.  held_bytes: what the three node
+// slots hold now (free memory the cache has already taken).
+inline size_t cache_quarter(size_t free_bytes, size_t held_bytes) { return (free_bytes + held_bytes) / 4; }
+
+// Bytes of the three node slots (both aggregators' and the spare) of nl nodes each.
+inline size_t node_slots_bytes(size_t nl, size_t node_words, size_t S1) { return 3 * nl * node_words * S1 * 4; }
+
+// The node format a cache-on call writes.  seeds / payloads: as asked,
+// whatever the memory.  auto: payloads if and only if all three slots, at
+// payload width and at the capacity this level's nl nodes need, fit the
+// cache's quarter of (free HBM + what the slots hold now); seeds if the
+// free-memory query failed.  More free memory never turns payloads into
+// seeds, more reports (S1) or nodes never seeds into payloads.
+inline int choose_node_words(int mode, size_t nl, size_t wlw, size_t S1, std::optional<size_t> free_bytes,
+                             size_t held_bytes) {
+    const int nw = payload_node_words(wlw);
+    if (mode == FC_NODES_PAYLOADS) return nw;
+    if (mode != FC_NODES_AUTO || !free_bytes) return SEED_NODE_WORDS;
+    return node_slots_bytes(nl, (size_t)nw, S1) <= cache_quarter(*free_bytes, held_bytes) ? nw : SEED_NODE_WORDS;
+}
+
+// Words per plane row of a new spare slot that must hold nl nodes of
+// node_words (slot_holds(spare_words, ...) is false): spare_capacity's growth
+// at that width.  bounded (auto chose payloads): the growth beyond the need
+// stops where three such slots would leave the cache's quarter.
+inline size_t spare_slot_words(size_t nl, size_t node_words, size_t spare_words, std::optional<size_t> free_bytes,
+                               size_t S1, bool bounded = false, size_t held_bytes = 0) {
+    size_t cap = spare_capacity(nl, spare_words / node_words, free_bytes, S1, node_words);
+    if (bounded && free_bytes)
+        cap = std::min(cap, std::max(nl, cache_quarter(*free_bytes, held_bytes) / 3 / (node_words * S1 * 4)));
+    return cap * node_words;
 }
 
 // -------------------------------------------------------------------- chunking

@@ -213,7 +213,10 @@ inline int last_level_segments(const SchedKnobs& c, const TreeShape& t, int grou
 // ------------------------------------------------------------------- the plan
 // Level-kernel instantiations (kernels.hpp eval_aes_body's GEN / FC / SPLIT /
 // WIDE), as a bit set.  The legal ones: FC only with GEN and nothing else.
-enum LevelVariant : int { LV_GEN = 1, LV_FC = 2, LV_SPLIT = 4, LV_WIDE = 8 };
+// (LV_PAY is not the plan's: the launch adds it to an FC launch whose input or
+// output cache slot holds payloads-format nodes, memplan.hpp.)
+enum LevelVariant : int { LV_GEN = 1, LV_FC = 2, LV_SPLIT = 4, LV_WIDE = 8, LV_PAY = 16 };
+constexpr int LV_FC_PAY = LV_GEN | LV_FC | LV_PAY;
 constexpr int LEVEL_VARIANTS[9] = {LV_GEN | LV_FC,
                                    0,       LV_GEN,           LV_SPLIT,           LV_GEN | LV_SPLIT,
                                    LV_WIDE, LV_WIDE | LV_GEN, LV_WIDE | LV_SPLIT, LV_WIDE | LV_GEN | LV_SPLIT};

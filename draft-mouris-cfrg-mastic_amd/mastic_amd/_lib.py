@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libmastic_hip.so")
 # The library lib() loads: always the shipped in-tree build, unless an A/B tool
 # calls load(path) explicitly (no process variable can swap it).
 LOAD_PATH = LIB_PATH
-ABI_VERSION = 7  # include/mastic_hip.h MASTIC_ABI_VERSION
+ABI_VERSION = 8  # include/mastic_hip.h MASTIC_ABI_VERSION
 
 MASTIC_OK = 0
 ERRORS = {-22: "EINVAL", -12: "ENOMEM", -19: "ENODEV", -5: "EHIP", -110: "ETIMEDOUT"}
@@ -32,6 +32,7 @@ EXPORTS = [
     "mastic_synchronize", "mastic_prep_init_batch", "mastic_decide_batch",
     "mastic_shard_batch", "mastic_last_timing", "mastic_tree_stats", "mastic_fold_shares",
     "mastic_work_bytes", "mastic_last_timing3", "mastic_proof_tree", "mastic_set_frontier_cache",
+    "mastic_set_frontier_cache_nodes",
     "mastic_reports_view", "mastic_decide_results",
     "mastic_aggregate_device_on_stream", "mastic_abi_version", "mastic_set_test_hooks",
     "mastic_set_test_sponge_delay", "mastic_set_serial_sponges", "mastic_set_last_level_segments",
@@ -167,6 +168,8 @@ def lib():
                     "mastic_work_bytes": (i32, [P, u8p, sz, ctypes.POINTER(ctypes.c_uint64)]),
                     "mastic_proof_tree": (i32, [P, ctypes.c_int, u8p, sz, P, sz]),
                     "mastic_set_frontier_cache": (i32, [P, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+                    "mastic_set_frontier_cache_nodes": (i32, [P, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                                              ctypes.POINTER(ctypes.c_int)]),
                     "mastic_tree_stats": (i32, [P, u8p, sz, ctypes.POINTER(ctypes.c_uint64),
                                                 ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
                 }

@@ -118,7 +118,25 @@ class SweepLevel:
 
 def compute_heavy_hitters(mastic: Mastic, ctx: bytes, thresholds, reports, verify_key: bytes = None,
                           trace=None, merge=None, timing=None, frontier_cache=None, cached_levels=None,
-                          phase_times=None, level_hook=None):
+                          phase_times=None, level_hook=None, cache_nodes=None):
+    """:func:`_sweep` (which documents the other arguments) with the frontier
+    cache's node format ``cache_nodes`` (``'seeds'``, ``'payloads'`` or
+    ``'auto'``: ``Mastic.set_frontier_cache_nodes``) set before the sweep and
+    left as found afterwards; None leaves the mastic's mode alone."""
+    if cache_nodes is None:
+        return _sweep(mastic, ctx, thresholds, reports, verify_key, trace, merge, timing, frontier_cache,
+                      cached_levels, phase_times, level_hook)
+    found = mastic.set_frontier_cache_nodes(cache_nodes)
+    try:
+        return _sweep(mastic, ctx, thresholds, reports, verify_key, trace, merge, timing, frontier_cache,
+                      cached_levels, phase_times, level_hook)
+    finally:
+        mastic.set_frontier_cache_nodes(found)
+
+
+def _sweep(mastic: Mastic, ctx: bytes, thresholds, reports, verify_key: bytes = None,
+           trace=None, merge=None, timing=None, frontier_cache=None, cached_levels=None,
+           phase_times=None, level_hook=None):
     """poc/examples.py:37-91 on the GPU.
 
     ``reports`` is either the reference's list of

@@ -449,6 +449,36 @@ class Mastic:
         _check(self._ctx, _lib.lib().mastic_set_frontier_cache(self._ctx, -1, ctypes.byref(v)))
         return bool(v.value)
 
+    CACHE_NODES = ("seeds", "payloads", "auto")  # MASTIC_FC_NODES_*
+
+    def set_frontier_cache_nodes(self, mode=None) -> str:
+        """The format of the frontier cache's nodes
+        (``mastic_set_frontier_cache_nodes``): ``'seeds'`` (the default: 20 B
+        per node, a hit re-runs each parent's convert stream), ``'payloads'``
+        (the node keeps its next seed and payload, a hit recomputes nothing) or
+        ``'auto'`` (payloads where the three node slots fit the cache's quarter
+        of the free HBM); None only queries.  A slot keeps the format it was
+        written in and a hit reads either, so changing the mode never drops
+        the cache.  Results are identical in every mode.  Returns the previous
+        mode."""
+        if mode is not None and mode not in self.CACHE_NODES:
+            raise ValueError("cache nodes mode must be one of %s" % (self.CACHE_NODES,))
+        rc = _lib.lib().mastic_set_frontier_cache_nodes(
+            self._ctx, -1 if mode is None else self.CACHE_NODES.index(mode), None, None)
+        if rc < 0:
+            _check(self._ctx, rc)
+        return self.CACHE_NODES[rc]
+
+    def last_cache_nodes(self):
+        """``(in, out)`` of the last prep_init: the node format its cache hit
+        read and the format it wrote into the cache, each ``'seeds'``,
+        ``'payloads'`` or None (not a hit / nothing written)."""
+        vin, vout = ctypes.c_int(), ctypes.c_int()
+        rc = _lib.lib().mastic_set_frontier_cache_nodes(self._ctx, -1, ctypes.byref(vin), ctypes.byref(vout))
+        if rc < 0:
+            _check(self._ctx, rc)
+        return tuple(None if v.value < 0 else self.CACHE_NODES[v.value] for v in (vin, vout))
+
     def proof_tree(self, agg_id: int, ctx: bytes, n: int):
         """Merkle tree over the eval proofs of the last prep_init of agg_id
         over n reports (proof-aggregation mode, see mastic_amd.proof_agg):

@@ -59,8 +59,10 @@ extern "C" {
  *    (test hook).
  * 7: mastic_set_last_level_segments (the last level of a prep_init evaluated
  *    in parent ranges, so its node proofs and binder sponges follow range by
- *    range instead of after the whole level). */
-#define MASTIC_ABI_VERSION 7
+ *    range instead of after the whole level).
+ * 8: mastic_set_frontier_cache_nodes (the frontier cache keeps node payloads
+ *    where asked or where HBM allows, so a hit skips the recompute). */
+#define MASTIC_ABI_VERSION 8
 
 #define MASTIC_OK 0
 #define MASTIC_EINVAL (-22)
@@ -290,6 +292,27 @@ int mastic_proof_tree(mastic_ctx* ctx, int agg_id, const uint8_t* app_ctx, size_
  * are identical either way.  *last_hit (if not NULL) = 1 when the last
  * prep_init took the cached path. */
 int mastic_set_frontier_cache(mastic_ctx* ctx, int on, int* last_hit);
+/* The format of the frontier cache's nodes.  SEEDS (the default): a node is
+ * its convert seed and control bit (20 B), and a hit re-runs each parent's
+ * convert stream for its next seed and payload.  PAYLOADS: a node is its next
+ * seed, control bit and corrected payload (20 B + VALUE_LEN field elements),
+ * and a hit recomputes nothing; if the wider slot cannot be allocated the call
+ * writes seeds.  AUTO: payloads if and only if the three node slots at that
+ * width fit a quarter of the free HBM (plus what they hold already), the share
+ * the work arena's budget leaves to the cache (csrc/memplan.hpp
+ * choose_node_words); seeds if the free-memory query fails.  The mode is that
+ * of the ctx and is read by every cache-on prep_init for the slot it writes; a
+ * slot keeps the format it was written in and a hit reads either, so changing
+ * the mode never drops the cache (mastic_set_frontier_cache(ctx, 0, ...)
+ * releases the slots).  Results are identical in every mode.
+ * mode < 0: query only.  Returns the previous mode, or MASTIC_EINVAL.
+ * last_in / last_out (may be NULL): the node format the last prep_init's hit
+ * read and the format that call wrote into the cache (-1: not a hit / nothing
+ * written). */
+#define MASTIC_FC_NODES_SEEDS 0
+#define MASTIC_FC_NODES_PAYLOADS 1
+#define MASTIC_FC_NODES_AUTO 2
+int mastic_set_frontier_cache_nodes(mastic_ctx* ctx, int mode, int* last_in, int* last_out);
 /* Measurement schedule: on = 1 makes every binder-sponge launch run alone
  * (the level kernels wait for it instead of running beside it), so the
  * sponge kernels' and the level kernel's own rates can be timed

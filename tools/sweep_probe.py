@@ -4,7 +4,11 @@ Wraps the Mastic calls the sweep driver makes (prep_init_device x2,
 decide_results, aggregate_device x2) with wall-clock timers and prints, per
 level: candidates, whether the frontier cache hit, the host time spent inside
 each call, the GPU time of each prep_init (HIP events) and the level's wall
-time.  GPU box only:  python3 tools/sweep_probe.py [n_reports]
+time.  The optional second argument is the frontier cache's node format
+(Mastic.set_frontier_cache_nodes: seeds, payloads or auto; default: the
+library's); the table shows per level the format each aggregator's hit read
+and the format its call wrote (s = seeds, p = payloads, - = none).
+GPU box only:  python3 tools/sweep_probe.py [n_reports [seeds|payloads|auto]]
 """
 import os
 import sys
@@ -22,6 +26,7 @@ from mastic_amd.heavy_hitters import compute_heavy_hitters  # noqa: E402
 
 def main():
     n_rep = int(sys.argv[1]) if len(sys.argv) > 1 else 1000000
+    nodes = sys.argv[2] if len(sys.argv) > 2 else None
     if os.environ.get("PROBE_TORCH") == "1":  # the bench's process state: torch's HIP context first
         import torch
         torch.cuda.synchronize()
@@ -60,6 +65,7 @@ def main():
             cur[name] = cur.get(name, 0.0) + time.perf_counter() - t
             if name == "prep_init_device":
                 cur["cached"] = cur.get("cached", 0) + int(m.last_prep_was_cached())
+                cur.setdefault("nodes", []).append(m.last_cache_nodes())
             return r
         setattr(m, name, g)
 
@@ -83,17 +89,20 @@ def main():
     tr = Trace()
     t0 = time.perf_counter()
     hh = compute_heavy_hitters(m, ctx, {"default": threshold}, reps, verify_key=vk, trace=tr, timing=timing,
-                               frontier_cache=True)
+                               frontier_cache=True, cache_nodes=nodes)
     m.synchronize()
     total = time.perf_counter() - t0
-    print("level cands cached  prep0+1_host  decide  agg   gpu_prep_ms(a0,a1)  wall_ms")
+    print("cache nodes mode: %s" % (nodes or m.set_frontier_cache_nodes()))
+    print("level cands cached  prep0+1_host  decide  agg   gpu_prep_ms(a0,a1)  wall_ms  nodes(in>out a0,a1)")
+    short = {None: "-", "seeds": "s", "payloads": "p"}
     for i, r in enumerate(rows):
         g = timing[2 * i:2 * i + 2]
         gp = [x[6] for x in g]  # total ms of each aggregator's prep_init (HIP events)
-        print("%5d %5d %6d %12.1f %7.1f %5.1f   %8.1f %8.1f %9.1f" % (
+        fm = " ".join("%s>%s" % (short[a], short[b]) for (a, b) in r.get("nodes", []))
+        print("%5d %5d %6d %12.1f %7.1f %5.1f   %8.1f %8.1f %9.1f  %s" % (
             r["level"], r["cands"], r.get("cached", 0), 1e3 * r.get("prep_init_device", 0),
             1e3 * r.get("decide_results", 0), 1e3 * r.get("aggregate_device", 0),
-            gp[0] if gp else 0, gp[1] if len(gp) > 1 else 0, 1e3 * r["wall"]))
+            gp[0] if gp else 0, gp[1] if len(gp) > 1 else 0, 1e3 * r["wall"], fm))
     print("total %.2f s, %d heavy hitters, timing tuple example %s" % (total, len(hh), timing[:1]))
 
 
