@@ -9,6 +9,8 @@
 // which equals interpolate-then-evaluate exactly (same polynomial, exact field
 // arithmetic) while touching only the CALLS + 1 non-zero wire values.
 #pragma once
+#include <vector>
+
 #include "field.hpp"
 #include "params.hpp"
 
@@ -61,6 +63,41 @@ struct FlpConsts {
     typename F::E offset;     // Sum / Multihot offset as a field element
     typename F::E offset_h;   // offset * inv2
 };
+
+// The constants of parameter set p (host).
+template <class F>
+inline FlpConsts<F> flp_consts(const McParams& p) {
+    typedef typename F::E E;
+    FlpConsts<F> fc;
+    // gen = 7^GEN_BASE_EXP; alpha = gen^(GEN_ORDER / P)
+    const uint64_t gen_exp = p.field == 64 ? 4294967295ull : 4611686018427387897ull;
+    E g = fpow_u64<F>(F::from_u64(7), gen_exp);
+    int log_order = FieldConsts<F>::GEN_ORDER_LOG2;
+    int logp = 0;
+    while ((1 << logp) < p.P) logp++;
+    int sh = log_order - logp;  // exponent 2^sh
+    uint64_t ex[2] = {0, 0};
+    ex[sh / 64] = 1ull << (sh % 64);
+    fc.alpha = fpow<F>(g, ex, 2);
+    fc.inv_p = finv<F>(F::from_u64((uint64_t)p.P));
+    fc.inv2 = finv<F>(F::from_u64(2));
+    fc.offset = F::from_u64(p.offset);
+    fc.offset_h = F::mul(fc.offset, fc.inv2);
+    return fc;
+}
+
+// flp_prove's table alpha^-i, i < P (host).
+template <class F>
+inline std::vector<typename F::E> flp_alpha_inv_pows(const FlpConsts<F>& fc, int P) {
+    typedef typename F::E E;
+    std::vector<E> pows(P);
+    E ainv = finv<F>(fc.alpha), acc = F::from_u64(1);
+    for (int i = 0; i < P; i++) {
+        pows[i] = acc;
+        acc = F::mul(acc, ainv);
+    }
+    return pows;
+}
 
 // Inputs of gadget call k (1-based): emit(j, x_j) for j < arity.
 // m(i) reads the measurement (share) element i, jr(i) joint rand i.

@@ -461,27 +461,6 @@ static int build_prefixes(mastic_ctx* c, const uint8_t* app_ctx, size_t ctx_len,
     return 0;
 }
 
-template <class F>
-static FlpConsts<F> flp_consts(const McParams& p) {
-    typedef typename F::E E;
-    FlpConsts<F> fc;
-    // gen = 7^GEN_BASE_EXP; alpha = gen^(GEN_ORDER / P)
-    const uint64_t gen_exp = p.field == 64 ? 4294967295ull : 4611686018427387897ull;
-    E g = fpow_u64<F>(F::from_u64(7), gen_exp);
-    int log_order = FieldConsts<F>::GEN_ORDER_LOG2;
-    int logp = 0;
-    while ((1 << logp) < p.P) logp++;
-    int sh = log_order - logp;  // exponent 2^sh
-    uint64_t ex[2] = {0, 0};
-    ex[sh / 64] = 1ull << (sh % 64);
-    fc.alpha = fpow<F>(g, ex, 2);
-    fc.inv_p = finv<F>(F::from_u64((uint64_t)p.P));
-    fc.inv2 = finv<F>(F::from_u64(2));
-    fc.offset = F::from_u64(p.offset);
-    fc.offset_h = F::mul(fc.offset, fc.inv2);
-    return fc;
-}
-
 // ---------------------------------------------------------------- tree
 // Decode Mastic.encode_agg_param (mastic.py:413-435) and build the evaluated
 // prefix tree of eval_with_siblings (vidpf.py:213-261): the children of every
@@ -2394,12 +2373,7 @@ static int shard_impl(mastic_ctx* c, mastic_reports* rep, const uint8_t* alphas,
     HIPCHK(c, hipMemcpy(dr.p, rands, rs * n, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(rep->nonces.p, nonces, 16 * n, hipMemcpyHostToDevice));
     FlpConsts<F> fc = flp_consts<F>(p);
-    std::vector<E> pows(p.P);
-    E ainv = finv<F>(fc.alpha), acc = F::from_u64(1);
-    for (int i = 0; i < p.P; i++) {
-        pows[i] = acc;
-        acc = F::mul(acc, ainv);
-    }
+    const std::vector<E> pows = flp_alpha_inv_pows<F>(fc, p.P);
     HIPCHK(c, hipMemcpy(tab.p, pows.data(), sizeof(E) * p.P, hipMemcpyHostToDevice));
     // scratch planes per report
     const size_t wl = (size_t)p.value_len * p.w32;

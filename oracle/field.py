@@ -113,36 +113,47 @@ class Field128(_Field):
 
 # --- polynomial helpers used by the FLP (restating vdaf_poc.polynomial) ---
 
+# (the inner loops run on Python integers: an element object per step made the
+# oracle side of the FLP grid tests several times slower)
+
 def poly_eval(field, poly, x):
-    acc = field(0)
+    p = field.MODULUS
+    xv = x.val
+    acc = 0
     for c in reversed(poly):
-        acc = acc * x + c
-    return acc
+        acc = (acc * xv + c.val) % p
+    return field(acc)
 
 
 def poly_mul(field, a, b):
-    out = [field(0) for _ in range(len(a) + len(b) - 1)]
+    p = field.MODULUS
+    out = [0] * (len(a) + len(b) - 1)
+    bv = [x.val for x in b]
     for (i, ai) in enumerate(a):
-        if ai.val == 0:
+        av = ai.val
+        if av == 0:
             continue
-        for (j, bj) in enumerate(b):
-            out[i + j] += ai * bj
-    return out
+        for (j, bj) in enumerate(bv):
+            out[i + j] += av * bj
+    return [field(x % p) for x in out]
 
 
 def poly_interp_roots_of_unity(field, alpha, ys):
     """Coefficients of the unique poly of degree < n with p(alpha^k) = ys[k],
     n = len(ys), alpha a primitive n-th root of unity (inverse DFT)."""
+    p = field.MODULUS
     n = len(ys)
-    n_inv = field(n).inv()
-    alpha_inv = alpha.inv()
+    n_inv = field(n).inv().val
+    alpha_inv = alpha.inv().val
+    # alpha^-m for m < n; the exponent i * k is taken mod n
+    pows = [1] * n
+    for m in range(1, n):
+        pows[m] = pows[m - 1] * alpha_inv % p
+    nz = [(k, y.val) for (k, y) in enumerate(ys) if y.val]
     coeffs = []
     for i in range(n):
-        w = alpha_inv ** i
-        acc = field(0)
-        wk = field(1)
-        for k in range(n):
-            acc += ys[k] * wk
-            wk = wk * w
-        coeffs.append(acc * n_inv)
+        acc = 0
+        for (k, y) in nz:
+            acc += y * pows[i * k % n]
+        coeffs.append(field(acc % p * n_inv % p))
     return coeffs
