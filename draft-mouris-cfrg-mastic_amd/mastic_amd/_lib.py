@@ -39,6 +39,8 @@ EXPORTS = [
     "mastic_comm_unique_id", "mastic_comm_init", "mastic_comm_init_timeout", "mastic_comm_info",
     "mastic_comm_destroy",
     "mastic_allgather_fold", "mastic_aggregate_merged", "mastic_merge_host",
+    "mastic_nonce_set_create", "mastic_nonce_set_destroy", "mastic_nonce_set_count", "mastic_nonce_set_admit",
+    "mastic_nonce_set_admit_reports", "mastic_nonce_set_contains", "mastic_nonce_set_export",
 ]
 COMM_ID_BYTES = 128  # MASTIC_COMM_ID_BYTES (= RCCL's NCCL_UNIQUE_ID_BYTES)
 ROCM_PATH = "/opt/rocm"  # the image's ROCm (the library dlopens librccl.so.1 from its lib/ on first comm use)
@@ -172,6 +174,13 @@ def lib():
                                                               ctypes.POINTER(ctypes.c_int)]),
                     "mastic_tree_stats": (i32, [P, u8p, sz, ctypes.POINTER(ctypes.c_uint64),
                                                 ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+                    "mastic_nonce_set_create": (i32, [P, sz, u8p, ctypes.POINTER(P)]),
+                    "mastic_nonce_set_destroy": (None, [P]),
+                    "mastic_nonce_set_count": (sz, [P]),
+                    "mastic_nonce_set_admit": (i32, [P, P, sz, P, ctypes.POINTER(sz)]),
+                    "mastic_nonce_set_admit_reports": (i32, [P, P, P, ctypes.POINTER(sz)]),
+                    "mastic_nonce_set_contains": (i32, [P, P, sz, P]),
+                    "mastic_nonce_set_export": (i32, [P, P, sz, ctypes.POINTER(sz)]),
                 }
                 for name, (res, args) in sig.items():
                     fn = getattr(l, name)

@@ -118,25 +118,25 @@ class SweepLevel:
 
 def compute_heavy_hitters(mastic: Mastic, ctx: bytes, thresholds, reports, verify_key: bytes = None,
                           trace=None, merge=None, timing=None, frontier_cache=None, cached_levels=None,
-                          phase_times=None, level_hook=None, cache_nodes=None):
+                          phase_times=None, level_hook=None, cache_nodes=None, nonce_set=None):
     """:func:`_sweep` (which documents the other arguments) with the frontier
     cache's node format ``cache_nodes`` (``'seeds'``, ``'payloads'`` or
     ``'auto'``: ``Mastic.set_frontier_cache_nodes``) set before the sweep and
     left as found afterwards; None leaves the mastic's mode alone."""
     if cache_nodes is None:
         return _sweep(mastic, ctx, thresholds, reports, verify_key, trace, merge, timing, frontier_cache,
-                      cached_levels, phase_times, level_hook)
+                      cached_levels, phase_times, level_hook, nonce_set)
     found = mastic.set_frontier_cache_nodes(cache_nodes)
     try:
         return _sweep(mastic, ctx, thresholds, reports, verify_key, trace, merge, timing, frontier_cache,
-                      cached_levels, phase_times, level_hook)
+                      cached_levels, phase_times, level_hook, nonce_set)
     finally:
         mastic.set_frontier_cache_nodes(found)
 
 
 def _sweep(mastic: Mastic, ctx: bytes, thresholds, reports, verify_key: bytes = None,
            trace=None, merge=None, timing=None, frontier_cache=None, cached_levels=None,
-           phase_times=None, level_hook=None):
+           phase_times=None, level_hook=None, nonce_set=None):
     """poc/examples.py:37-91 on the GPU.
 
     ``reports`` is either the reference's list of
@@ -157,6 +157,18 @@ def _sweep(mastic: Mastic, ctx: bytes, thresholds, reports, verify_key: bytes = 
     accumulated into it (seconds).  ``level_hook(level, enc_agg_param, reports)``
     (if given) runs after each level's decide, while both aggregators' prep_init
     results of the level are still in HBM (e.g. to read sampled prep shares).
+
+    ``nonce_set`` (a :class:`~mastic_amd.nonce_set.NonceSet`, or any object
+    with ``admit(reports) -> mask``) is the aggregator's replay protection:
+    the sweep begins by admitting the batch, and a report whose nonce the set
+    already held, or that occurs earlier in the batch, is dropped from every
+    level exactly like a report that fails verification, so the counts and
+    ``num_measurements`` cover fresh reports only.  Afterwards the set holds
+    the batch's nonces, so sweeping the same reports again with the same set
+    keeps none of them.  Multi-rank: each rank's set sees only its own shard,
+    so a job gets job-wide protection only if it routes every report to a rank
+    by its nonce (copies of a report then meet in one set); the routing is the
+    job's business.
     """
     def clock(phase, t0):
         if phase_times is not None:
@@ -179,6 +191,8 @@ def _sweep(mastic: Mastic, ctx: bytes, thresholds, reports, verify_key: bytes = 
         dev = reports
     n = 0 if dev is None else dev.n
     alive = np.ones(n, dtype=bool)
+    if nonce_set is not None and n:
+        alive = np.asarray(nonce_set.admit(dev)) == 1
 
     prefixes = [(False,), (True,)]
     fast = isinstance(mastic, Mastic)

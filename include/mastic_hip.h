@@ -61,7 +61,9 @@ extern "C" {
  *    in parent ranges, so its node proofs and binder sponges follow range by
  *    range instead of after the whole level).
  * 8: mastic_set_frontier_cache_nodes (the frontier cache keeps node payloads
- *    where asked or where HBM allows, so a hit skips the recompute). */
+ *    where asked or where HBM allows, so a hit skips the recompute).
+ * Still 8: the replay set (mastic_nonce_set_*) is additive, seven new entry
+ *    points and no change to an existing one, so the version stays. */
 #define MASTIC_ABI_VERSION 8
 
 #define MASTIC_OK 0
@@ -137,6 +139,47 @@ int mastic_reports_view(mastic_reports* rep, size_t first, size_t count, mastic_
  * nonces n*16, rands n*rand_size. */
 int mastic_reports_shard(mastic_reports* rep, const uint8_t* app_ctx, size_t ctx_len, const uint8_t* alphas,
                          const uint8_t* betas, const uint8_t* nonces, const uint8_t* rands);
+
+/* ---- replay protection: the nonces an aggregator has admitted ---------
+ * (No counterpart in the reference, whose driver handles 13 reports.)  A set
+ * of 16-byte nonces in the HBM of the ctx's GPU.  Admitting a batch
+ * x_0..x_{n-1} into a set S gives fresh[i] = 1 iff x_i was not in S before the
+ * call and x_j != x_i for every j < i (the first occurrence in the batch wins,
+ * by report index), and leaves S = S u {x_i}.  The result is a function of the
+ * set's contents and the batch only, not of the hash key, the table's size or
+ * how the GPU schedules the call.  A report whose fresh flag is 0 is a replay:
+ * drop it like a report that fails verification (clear its entry of the valid
+ * mask given to mastic_aggregate).
+ * Memory: 16 B per nonce for the key, 8 to 16 B for the hash table (a power of
+ * two of 4-byte slots, never more than half full), so at most 32 B per nonce
+ * above the 12 KiB minimum, plus 21 B per nonce of the largest batch as scratch
+ * (16 of them only for host nonces).  hash_key is the 128-bit secret of the
+ * table's keyed hash (clients choose their nonces; NULL: drawn from the
+ * operating system); capacity_hint sizes the set for that many nonces up
+ * front (0: the minimum; it grows as needed).  A set is destroyed before its
+ * ctx and is, like the ctx, thread-compatible.  Every call blocks.
+ * Failure atomicity: an admit allocates everything it needs before it changes
+ * the set, so after MASTIC_ENOMEM the set is as it was and the same call may be
+ * repeated.  MASTIC_EHIP from an admit or a query means the set's state is no
+ * longer known; every later call on it fails the same way.  At most 2^30
+ * nonces per set (MASTIC_EINVAL beyond). */
+typedef struct mastic_nonce_set mastic_nonce_set;
+int mastic_nonce_set_create(mastic_ctx* ctx, size_t capacity_hint, const uint8_t hash_key[16], mastic_nonce_set** out);
+void mastic_nonce_set_destroy(mastic_nonce_set* set);
+size_t mastic_nonce_set_count(const mastic_nonce_set* set);
+/* Admit n host nonces (n*16 bytes).  fresh_out (n) and n_fresh may be NULL. */
+int mastic_nonce_set_admit(mastic_nonce_set* set, const uint8_t* nonces, size_t n, uint8_t* fresh_out,
+                           size_t* n_fresh);
+/* Admit the nonces of a resident batch, or of a view's own rows, of the set's
+ * ctx (MASTIC_EINVAL otherwise): they are read where they lie in HBM. */
+int mastic_nonce_set_admit_reports(mastic_nonce_set* set, mastic_reports* rep, uint8_t* fresh_out, size_t* n_fresh);
+/* found_out[i] = 1 iff nonce i is in the set; nothing is inserted. */
+int mastic_nonce_set_contains(mastic_nonce_set* set, const uint8_t* nonces, size_t n, uint8_t* found_out);
+/* The set's nonces (checkpoint), in no specified order: *n_out (may be NULL)
+ * = their number, always; the nonces are written if capacity (in nonces) is
+ * at least that, MASTIC_EINVAL otherwise.  Restoring is mastic_nonce_set_admit
+ * of these bytes into a new set. */
+int mastic_nonce_set_export(mastic_nonce_set* set, uint8_t* nonces_out, size_t capacity, size_t* n_out);
 
 /* ---- aggregator preparation ----------------------------------------- */
 /* Enqueue prep_init for every report of `rep` as aggregator agg_id.
