@@ -26,10 +26,12 @@
 #include <vector>
 
 #include "comm_agree.hpp"
+#include "compact_plan.hpp"
 #include "host_tree.hpp"
 #include "kernels.hpp"
 #include "memplan.hpp"
 #include "nonce_set_kernels.hpp"
+#include "rows_kernels.hpp"
 #include "schedule.hpp"
 #include "shard.hpp"
 
@@ -2463,6 +2465,84 @@ extern "C" int mastic_shard_batch(mastic_ctx* c, const uint8_t* app_ctx, size_t 
     if (!rc) rc = mastic_reports_download(rep, nullptr, pub_out, in0_out, in1_out);
     mastic_reports_destroy(rep);
     return rc;
+}
+
+// ---------------------------------------------------------------- compaction
+// mastic_reports_compact: the plan is compact_plan.hpp, the kernel
+// rows_kernels.hpp.  Everything runs on the ctx's main stream.  That orders it
+// after every queued reader of the batch's buffers, because all of them run
+// there: k_unpack, k_rows_to_planes and k_validate_wire (Chunk::unpack and
+// validate_wire launch on c->stream whatever stream the chunk's sponges use),
+// k_shard and the replay set's kernels.  Streams 2 to 4 run binder sponges and
+// the FLP query, which read the work arena only, so no event is needed.
+static int compact_segment(mastic_ctx* c, uint8_t* seg, size_t rb, const CompactIndex& ix, const uint32_t* d_idx,
+                           uint8_t* stage, size_t stage_bytes) {
+    const size_t S = compact_stage_rows(stage_bytes, rb);
+    for (const CompactLaunch& l : compact_launches(ix, S)) {
+        if (l.op == CP_COPY_BACK) {
+            HIPCHK(c, hipMemcpyAsync(seg + l.first * rb, stage, l.count * rb, hipMemcpyDeviceToDevice, c->stream));
+            continue;
+        }
+        uint8_t* dst = l.op == CP_GATHER_STAGE ? stage : seg + l.first * rb;
+        // (one launch's grid.x is bounded; a tile above it goes out in pieces, in order)
+        const size_t piece = std::max<size_t>(1, (size_t)(ROWS_MAX_GRID * ROWS_THREADS / rows_slots_per_row(rb)));
+        for (size_t o = 0; o < l.count; o += piece) {
+            const size_t cnt = std::min(piece, l.count - o);
+            hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)rows_grid(rb, cnt)), dim3(ROWS_THREADS), 0, c->stream,
+                               (const uint8_t*)seg, dst + o * rb, rb, d_idx, l.first + o, cnt, rows_slots_per_row(rb));
+            HIPCHK(c, hipGetLastError());
+        }
+    }
+    return 0;
+}
+
+extern "C" int mastic_reports_compact(mastic_reports* rep, const uint8_t* keep, size_t staging_bytes, size_t* n_kept) {
+    DeviceScope ds_(rep ? rep->ctx : nullptr);
+    if (!rep) return MASTIC_EINVAL;
+    mastic_ctx* c = rep->ctx;
+    if (!rep->nonces.own || !rep->pub.own || !rep->wire_flags.own)
+        return fail(c, MASTIC_EINVAL, "compact: the batch is a view (compact the batch that owns the memory)");
+    if (!keep) return fail(c, MASTIC_EINVAL, "compact: null keep mask");
+    if (rep->n > 0xffffffffull) return fail(c, MASTIC_EINVAL, "compact: too many reports");
+    const CompactIndex ix = compact_index(keep, rep->n);
+    if (n_kept) *n_kept = ix.n_kept;
+    if (ix.n_kept == rep->n) return 0;  // nothing dropped: same contents, same generation
+    if (ix.moved() > 0) {
+        const McParams& p = c->p;
+        struct Seg {
+            DevBuf* b;
+            size_t rb;
+        } segs[5] = {{&rep->nonces, 16},
+                     {&rep->pub, (size_t)mc_public_share_size(p)},
+                     {&rep->in0, (size_t)mc_input_share_size(p, 0)},
+                     {&rep->in1, (size_t)mc_input_share_size(p, 1)},
+                     {&rep->wire_flags, 1}};
+        size_t widest = 0;
+        for (const Seg& s : segs)
+            if (s.b->p) widest = std::max(widest, s.rb);
+        const size_t sb = compact_staging_bytes(staging_bytes, widest, ix.moved());
+        // both allocations before any row moves: MASTIC_ENOMEM leaves the batch as it was
+        DevBuf d_idx, stage;
+        if (c->inject_alloc_failure() || !d_idx.ensure(4 * ix.n_kept) || !stage.ensure(sb))
+            return fail(c, MASTIC_ENOMEM, "out of device memory (compact: %zu B staging, %zu B index)", sb,
+                        4 * ix.n_kept);
+        int rc = 0;
+        if (hipMemcpyAsync(d_idx.p, ix.src.data(), 4 * ix.n_kept, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+            rc = fail(c, MASTIC_EHIP, "compact: the index upload failed");
+        for (const Seg& s : segs)
+            if (!rc && s.b->p)
+                rc = compact_segment(c, s.b->as<uint8_t>(), s.rb, ix, d_idx.as<uint32_t>(), stage.as<uint8_t>(), sb);
+        // (also on failure: the index and the staging buffer are freed on return)
+        if (hipStreamSynchronize(c->stream) != hipSuccess && !rc)
+            rc = fail(c, MASTIC_EHIP, "compact: the row moves failed; the batch must be uploaded again");
+        if (rc) {
+            rep->touch();
+            return rc;
+        }
+    }
+    rep->touch();
+    rep->n = ix.n_kept;
+    return 0;
 }
 
 // ---------------------------------------------------------------- replay set

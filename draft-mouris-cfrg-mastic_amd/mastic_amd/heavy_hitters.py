@@ -118,25 +118,25 @@ class SweepLevel:
 
 def compute_heavy_hitters(mastic: Mastic, ctx: bytes, thresholds, reports, verify_key: bytes = None,
                           trace=None, merge=None, timing=None, frontier_cache=None, cached_levels=None,
-                          phase_times=None, level_hook=None, cache_nodes=None, nonce_set=None):
+                          phase_times=None, level_hook=None, cache_nodes=None, nonce_set=None, compact=None):
     """:func:`_sweep` (which documents the other arguments) with the frontier
     cache's node format ``cache_nodes`` (``'seeds'``, ``'payloads'`` or
     ``'auto'``: ``Mastic.set_frontier_cache_nodes``) set before the sweep and
     left as found afterwards; None leaves the mastic's mode alone."""
     if cache_nodes is None:
         return _sweep(mastic, ctx, thresholds, reports, verify_key, trace, merge, timing, frontier_cache,
-                      cached_levels, phase_times, level_hook, nonce_set)
+                      cached_levels, phase_times, level_hook, nonce_set, compact)
     found = mastic.set_frontier_cache_nodes(cache_nodes)
     try:
         return _sweep(mastic, ctx, thresholds, reports, verify_key, trace, merge, timing, frontier_cache,
-                      cached_levels, phase_times, level_hook, nonce_set)
+                      cached_levels, phase_times, level_hook, nonce_set, compact)
     finally:
         mastic.set_frontier_cache_nodes(found)
 
 
 def _sweep(mastic: Mastic, ctx: bytes, thresholds, reports, verify_key: bytes = None,
            trace=None, merge=None, timing=None, frontier_cache=None, cached_levels=None,
-           phase_times=None, level_hook=None, nonce_set=None):
+           phase_times=None, level_hook=None, nonce_set=None, compact=None):
     """poc/examples.py:37-91 on the GPU.
 
     ``reports`` is either the reference's list of
@@ -169,7 +169,24 @@ def _sweep(mastic: Mastic, ctx: bytes, thresholds, reports, verify_key: bytes = 
     so a job gets job-wide protection only if it routes every report to a rank
     by its nonce (copies of a report then meet in one set); the routing is the
     job's business.
+
+    ``compact`` (None, or a float t in [0, 1]) drops dead reports from the
+    resident batch itself (``Reports.compact``), so that later levels do not
+    evaluate them: None, the default, never does.  With t, the batch is
+    compacted when the dead share of the current batch is at least t, at
+    exactly two points: after the replay admit, before level 0, and after
+    level 0's fold.  That is where almost all rejections happen (replays, the
+    weight check, malformed shares), and the frontier-cache miss a compaction
+    forces re-evaluates a tree of 2 nodes there; later rejections stay masked,
+    because compacting then would turn a cache hit into a whole-tree miss.
+    Every level's aggregate, ``n_valid`` and ``num_measurements`` are the same
+    either way.  If ``reports`` is the caller's own :class:`Reports` batch,
+    compaction mutates it: afterwards it holds the surviving reports only, in
+    their order, and ``reports.n`` is their number.
     """
+    if compact is not None and not 0.0 <= compact <= 1.0:
+        raise ValueError("compact must be None or a share in [0, 1]")
+
     def clock(phase, t0):
         if phase_times is not None:
             t1 = time.perf_counter()
@@ -193,6 +210,17 @@ def _sweep(mastic: Mastic, ctx: bytes, thresholds, reports, verify_key: bytes = 
     alive = np.ones(n, dtype=bool)
     if nonce_set is not None and n:
         alive = np.asarray(nonce_set.admit(dev)) == 1
+
+    def drop_dead():
+        # the dead rows leave the batch; the survivors keep their order
+        nonlocal n, alive
+        dead = n - int(alive.sum())
+        if compact is None or dead == 0 or dead < compact * n:
+            return
+        n = dev.compact(alive)
+        alive = np.ones(n, dtype=bool)
+
+    drop_dead()
 
     prefixes = [(False,), (True,)]
     fast = isinstance(mastic, Mastic)
@@ -286,6 +314,8 @@ def _sweep(mastic: Mastic, ctx: bytes, thresholds, reports, verify_key: bytes = 
         prev_agg_params.append(agg_param)
         if trace is not None:
             trace.append(SweepLevel(level, list(prefixes), agg_result, int(alive.sum())))
+        if level == 0:
+            drop_dead()
 
         if lazy:
             if level < bits - 1:

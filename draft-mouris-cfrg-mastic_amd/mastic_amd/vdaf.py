@@ -740,6 +740,32 @@ class Reports:
             self._ptr, _lib.buf(nonces), _lib.buf(public_shares), _lib.buf(input_shares_0),
             _lib.buf(input_shares_1)))
 
+    def compact(self, keep, staging_bytes: int = 0) -> int:
+        """Keep the reports with ``keep[i] != 0``, in their order, as reports
+        0..k-1 of this batch, in place on the GPU (``mastic_reports_compact``);
+        returns k, which is ``self.n`` from then on.  A view cannot be
+        compacted; views and prep_init results made earlier keep the old
+        numbering.  ``staging_bytes`` bounds the extra device memory (0: the
+        library's default).  A mask that drops nothing leaves the batch, and
+        the frontier cache's entries for it, as they are.  Errors are
+        ``MasticError`` with the library's code (a view or ``keep=None``:
+        EINVAL; out of device memory: ENOMEM, the batch unchanged)."""
+        k = None
+        if keep is not None:
+            k = np.asarray(keep)
+            # the library tests bytes against 0: a bool or uint8 mask goes as it is
+            k = k.view(np.uint8) if k.dtype == np.bool_ else k if k.dtype == np.uint8 else (k != 0).view(np.uint8)
+            k = np.ascontiguousarray(k)
+        if k is not None and k.shape != (self.n,):
+            raise ValueError("keep must have one entry per report")
+        kept = ctypes.c_size_t()
+        rc = _lib.lib().mastic_reports_compact(self._ptr, _lib.buf(k), staging_bytes, ctypes.byref(kept))
+        if rc != 0:  # MasticError for every code: a view or a missing mask is EINVAL, not a bad value
+            msg = _lib.lib().mastic_last_error(self._m._ctx)
+            raise _lib.MasticError(rc, (msg or b"").decode(errors="replace") or "mastic error")
+        self.n = kept.value
+        return self.n
+
     def download(self):
         m = self._m
         n = self.n

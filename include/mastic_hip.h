@@ -63,7 +63,8 @@ extern "C" {
  * 8: mastic_set_frontier_cache_nodes (the frontier cache keeps node payloads
  *    where asked or where HBM allows, so a hit skips the recompute).
  * Still 8: the replay set (mastic_nonce_set_*) is additive, seven new entry
- *    points and no change to an existing one, so the version stays. */
+ *    points and no change to an existing one, so the version stays; so is
+ *    mastic_reports_compact. */
 #define MASTIC_ABI_VERSION 8
 
 #define MASTIC_OK 0
@@ -139,6 +140,35 @@ int mastic_reports_view(mastic_reports* rep, size_t first, size_t count, mastic_
  * nonces n*16, rands n*rand_size. */
 int mastic_reports_shard(mastic_reports* rep, const uint8_t* app_ctx, size_t ctx_len, const uint8_t* alphas,
                          const uint8_t* betas, const uint8_t* nonces, const uint8_t* rands);
+/* Keep the reports with keep[i] != 0 (keep has mastic_reports_count(rep)
+ * entries), in their order, as reports 0..n_kept-1 of `rep`, in place in HBM;
+ * mastic_reports_count(rep) becomes n_kept (*n_kept, may be NULL, receives
+ * it).  For dropping replays and rejected reports from the work of later
+ * prep_inits, not only from their sums.
+ * What moves: every segment the batch holds (nonces, public shares, whichever
+ * input shares exist) and the wire-check verdicts, so a moved report keeps its
+ * MASTIC_STATUS_NONCANONICAL.  `rep` must own its memory: a view, or
+ * keep == NULL, is MASTIC_EINVAL.  Rows n_kept and above are unspecified
+ * afterwards; the allocations stay, so mastic_reports_upload of n_kept rows
+ * works.  Views made earlier alias the same HBM, as with upload, and their row
+ * numbering is stale; results of earlier prep_inits keep the old numbering and
+ * the old n (result slots are not touched).
+ * If nothing is dropped the call does nothing: the contents generation stays,
+ * and a frontier-cache hit still follows.  Otherwise the batch counts as new
+ * contents (as after an upload): the next prep_init is a cache miss and derives
+ * its key schedules again.
+ * The call blocks.  Its work runs on the ctx's main stream, after every queued
+ * kernel that reads the batch (prep_init's unpack, the wire check, the shard
+ * and the replay set all run there).
+ * staging_bytes bounds the extra device memory: 0 selects the default (64 MiB),
+ * and it is raised to one row of the widest segment.  The call allocates that
+ * staging buffer (less, if the rows that move need less) and 4 B per kept
+ * report for the index, nothing else, whatever n is.  Both are allocated before
+ * any row moves (they take mastic_set_test_hooks' fail_allocs), so after
+ * MASTIC_ENOMEM the batch and its count are as they were and the same call may
+ * be repeated.  After MASTIC_EHIP the batch's contents are unspecified: upload
+ * it again. */
+int mastic_reports_compact(mastic_reports* rep, const uint8_t* keep, size_t staging_bytes, size_t* n_kept);
 
 /* ---- replay protection: the nonces an aggregator has admitted ---------
  * (No counterpart in the reference, whose driver handles 13 reports.)  A set
