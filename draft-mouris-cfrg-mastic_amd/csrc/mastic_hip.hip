@@ -218,19 +218,11 @@ struct mastic_ctx {
     // the running chunk's sponge ends: per planned sponge launch, and the last
     // piece of the one-hot / payload sponge of each level (run_plan)
     std::vector<hipEvent_t> sp_done, oh_done, pl_done;
-    int absorb_lds = 0;         // bytes of dynamic LDS per absorb workgroup (MASTIC_ABSORB_LDS_KB)
-    int proof_prio = 0;                  // s_setprio of the level kernel's proof waves (MASTIC_PROOF_PRIO)
-    int aes_prio = 0;                    // s_setprio of the AES waves (MASTIC_AES_PRIO)
-    bool binder_tiled = true;            // tiled level binder buffers (MASTIC_BINDER_TILED=0: planes)
-    int absorb_threads = 256;            // threads per binder-sponge workgroup (MASTIC_ABSORB_THREADS)
-    int absorb_prio = 3;                 // s_setprio of the binder sponge waves (MASTIC_ABSORB_PRIO)
-    int absorb_dbg = 0;                  // timing experiments only (MASTIC_ABSORB_DBG, kernels.hpp AbsorbArgs::dbg)
     // result-preserving test hooks (mastic_set_test_hooks; nothing in the environment sets them)
     int force_slow_blk = -1;    // exact payload stream from this block on
     int fail_allocs = 0;        // this many result / cache-slot allocations fail first (ENOMEM recovery)
     int sponge_delay_us = 0;    // the next prep_init first holds the sponge stream this long (k_spin)
     int wall_khz = 100000;      // wall_clock64() rate (hipDeviceAttributeWallClockRate)
-    bool timing_nowait = false; // A/B of the last_timing fix only (MASTIC_DBG_TIMING_NOWAIT, knob builds)
     bool serial_sponges = false;  // measurement: sponge launches run alone (mastic_set_serial_sponges)
     bool inject_alloc_failure() {
         if (fail_allocs <= 0) return false;
@@ -714,9 +706,10 @@ struct Chunk {
     // and the root sum in the cache's planes (same stride): a hit resumes and
     // updates them in place, a miss fills them; no copies in or out.
     bool direct;
-    // tiled level buffers (kernels.hpp AbsorbArgs): words per report group
-    // (MASTIC_BINDER_TILED=0: plane layout, i.e. group stride 64, row stride = stride)
-    int oh_gstride, pay_gstride, bin_rstride;
+    // tiled level buffers (kernels.hpp AbsorbArgs): words per report group,
+    // and between consecutive words of a report
+    int oh_gstride, pay_gstride;
+    static constexpr int bin_rstride = 64;
     int groups() const { return (n + 63) / 64; }  // report groups (rows beyond n are padding)
     int wlw() const { return c->p.value_len * c->p.w32; }
     uint32_t* plane(size_t off) const { return W + off * (size_t)stride; }
@@ -873,19 +866,19 @@ struct Chunk {
             ab.rstride = bin_rstride;
             ab.nbytes[1] = s.level > 0 ? s.piece.parents * wlw() * 4 : 0;
             ab.f[1] = s.f_pl;
-            ab.prio = c->absorb_prio;
-            ab.dbg = c->absorb_dbg;
+            // The priority and debug arguments of AbsorbArgs and AesArgs were
+            // experiment knobs; their A/Bs are settled and the executor pins the
+            // values.  The fields stay in kernels.hpp because taking them out
+            // moves the kernels' register allocation (DESIGN.md "Retired knobs").
+            ab.prio = 3;
+            ab.dbg = 0;
             if (as != c->stream) HIPCHK(c, hipStreamWaitEvent(as, ready, 0));
             if (m4) HIPCHK(c, hipEventRecord(m4, as));
-            if (c->k.dbg_skip & 4) {
-                // timing experiments only: no binder sponges (results wrong)
-            } else if (plan.pair)
-                hipLaunchKernelGGL(k_absorb_pair,
-                                   dim3((groups() * 64 * 2 + c->absorb_threads - 1) / c->absorb_threads, (unsigned)s.nwh),
-                                   dim3(c->absorb_threads), c->absorb_lds, as, pl, ab);
+            if (plan.pair)
+                hipLaunchKernelGGL(k_absorb_pair, dim3((groups() * 64 * 2 + 255) / 256, (unsigned)s.nwh), dim3(256), 0, as,
+                                   pl, ab);
             else
-                hipLaunchKernelGGL(k_absorb, dim3((groups() * 64 + 255) / 256, (unsigned)s.nwh), dim3(256),
-                                   c->absorb_lds, as, pl, ab);
+                hipLaunchKernelGGL(k_absorb, dim3((groups() * 64 + 255) / 256, (unsigned)s.nwh), dim3(256), 0, as, pl, ab);
             if (m5) HIPCHK(c, hipEventRecord(m5, as));
             HIPCHK(c, hipGetLastError());
             const hipEvent_t done = c->sp_done[i] = get_sync_event(c, sev++);
@@ -957,9 +950,7 @@ struct Chunk {
         a.cur_onehot = oh_buf(l);
         a.aes_waves = v.aes_waves;
         a.par_waves = v.par_waves;
-        a.proof_prio = c->proof_prio;
-        a.aes_prio = c->aes_prio;
-        a.dbg_skip = c->k.dbg_skip;
+        a.proof_prio = a.aes_prio = a.dbg_skip = 0;  // pinned (launch_sponges)
         // the proof job: level l-1's nodes (seeds in cs_in), or an earlier range
         // of this level's (the previous launch's cs_out)
         const size_t n0 = (size_t)v.pv_node0;
@@ -1111,9 +1102,8 @@ struct Chunk {
             pl.sp_payload = lc->sp.as<uint32_t>() + (size_t)50 * lc->S;
             pl.rootsum = lc->rootsum.as<uint32_t>();
         }
-        oh_gstride = c->binder_tiled ? t->max_level_nodes * 8 * 64 : 64;
-        pay_gstride = c->binder_tiled ? t->max_parents * wlw() * 64 : 64;
-        bin_rstride = c->binder_tiled ? 64 : stride;
+        oh_gstride = t->max_level_nodes * 8 * 64;
+        pay_gstride = t->max_parents * wlw() * 64;
         int rc = unpack();
         if (rc || (rc = setup()) || (rc = run_plan<F>()) || (rc = finish<F>())) return rc;
         if (evi - evi0 != (size_t)plan.n_timing || sev - sev0 != (size_t)plan.n_sync)
@@ -1179,12 +1169,12 @@ struct CacheUse {
     int out_nw = SEED_NODE_WORDS;   // words per node this call writes into cout
 };
 
-// Frontier cache (tiled binder buffers only): decide hit / miss and size the
-// slots.  Runs before the work arena is sized, so the HBM budget sees the cache.
+// Frontier cache: decide hit / miss and size the slots.  Runs before the work
+// arena is sized, so the HBM budget sees the cache.
 static CacheUse cache_slots(mastic_ctx* c, int agg_id, const Tree* t, const mastic_reports* rep,
                             const std::vector<uint8_t>& lkey) {
     CacheUse u;
-    if (!c->frontier_cache || !c->binder_tiled) {
+    if (!c->frontier_cache) {
         c->lc[agg_id].drop();
         return u;
     }
@@ -2142,8 +2132,7 @@ extern "C" int mastic_last_timing3(mastic_ctx* c, double* aes_ms, int* aes_launc
         // on the sponge stream while its sponges run on the main stream):
         // wait for the marks themselves (an unwaited mark gave "device not
         // ready" in a 4-rank run sharing one GPU)
-        if (!c->timing_nowait)
-            for (int i = 0; i < -c->tm[c->tcur].n_eval; i++) HIPCHK(c, hipEventSynchronize(c->tm[c->tcur].ev[i]));
+        for (int i = 0; i < -c->tm[c->tcur].n_eval; i++) HIPCHK(c, hipEventSynchronize(c->tm[c->tcur].ev[i]));
         // events: [t0, t1] then per level [aes0, aes1, proof0, proof1, absorb0, absorb1]
         const size_t evi = (size_t)(-c->tm[c->tcur].n_eval);
         double ta = 0, tp = 0, tb = 0;
@@ -2781,67 +2770,25 @@ extern "C" int mastic_ctx_create(const mastic_params* up, mastic_ctx** out) {
     }
 #ifdef MASTIC_EXPERIMENT_KNOBS
     // A/B and timing experiments only (tools/ab_*.sh build the library with
-    // -DMASTIC_EXPERIMENT_KNOBS; the shipped library reads none of these).
-    // MASTIC_DBG_SKIP and MASTIC_ABSORB_DBG skip or gut kernels: results wrong.
+    // -DMASTIC_EXPERIMENT_KNOBS; the shipped library reads none of these):
+    // the knobs that are still open and have no mastic_set_* entry point.
     {
         const char* e = getenv("MASTIC_ABSORB_SINGLE");
         if (e) c->k.absorb_mode = e[0] == '1' ? 1 : (e[0] == '2' ? 2 : 0);
         const char* esm = getenv("MASTIC_ABSORB_SINGLE_MIN");
         if (esm) c->k.absorb_single_min = (size_t)std::max(0, atoi(esm));
-        const char* l = getenv("MASTIC_ABSORB_LDS_KB");
-        c->absorb_lds = l ? std::max(0, std::min(160, atoi(l))) * 1024 : 0;
-        const char* pw = getenv("MASTIC_PROOF_WAVES");
-        if (pw) c->k.proof_waves = std::max(1, std::min(15, atoi(pw)));
         const char* spd = getenv("MASTIC_STRIDE_PAD");
         if (spd) c->m.stride_pad = std::max(0, std::min(1 << 20, atoi(spd))) / 64 * 64;
         const char* wa = getenv("MASTIC_WORK_ARENA_GB");
         if (wa) c->m.work_arena = c->m.work_arena_fc = (size_t)std::max(0, atoi(wa)) << 30;
-        const char* bt = getenv("MASTIC_BINDER_TILED");
-        if (bt) c->binder_tiled = bt[0] != '0';
-        const char* at = getenv("MASTIC_ABSORB_THREADS");
-        if (at) c->absorb_threads = std::max(64, std::min(256, atoi(at))) / 64 * 64;
-        const char* ap = getenv("MASTIC_ABSORB_PRIO");
-        if (ap) c->absorb_prio = std::max(0, std::min(3, atoi(ap)));
-        const char* adb = getenv("MASTIC_ABSORB_DBG");
-        if (adb) c->absorb_dbg = atoi(adb);
-        const char* dsk = getenv("MASTIC_DBG_SKIP");
-        if (dsk) c->k.dbg_skip = atoi(dsk);
-        const char* xp = getenv("MASTIC_AES_PRIO");
-        if (xp) c->aes_prio = std::max(0, std::min(2, atoi(xp)));
-        const char* pp = getenv("MASTIC_PROOF_PRIO");
-        if (pp) c->proof_prio = std::max(0, std::min(2, atoi(pp)));
-        const char* pw2 = getenv("MASTIC_PAR_WAVES");
-        if (pw2) c->k.par_waves = std::max(1, std::min(EVAL_WAVES, atoi(pw2)));
         const char* cp = getenv("MASTIC_CHUNK_PIPELINE");
         if (cp) c->m.chunk_pipeline = cp[0] != '0';
-        const char* hpw = getenv("MASTIC_HIT_PROOF_WAVES");
-        if (hpw) c->k.hit_proof_waves = std::max(0, std::min(15, atoi(hpw)));
         const char* fp = getenv("MASTIC_FUSE_PROOFS");
-        if (fp) c->k.fuse_proofs = std::max(0, std::min(3, atoi(fp)));
-        const char* fa = getenv("MASTIC_FC_ALL");
-        if (fa) c->k.fc_all = fa[0] == '1';
+        if (fp) c->k.fuse_proofs = atoi(fp) > 0;
         const char* cr = getenv("MASTIC_CHUNK_REPORTS");
         if (cr) c->m.chunk_max = (size_t)std::max(0, atoi(cr));
         const char* spl = getenv("MASTIC_SPLIT_SPONGES");
         if (spl) c->k.split_sponges = spl[0] == '1' ? 1 : 0;
-        const char* flm = getenv("MASTIC_FUSE_LAST_MISS");
-        if (flm) c->k.fuse_last_miss = flm[0] == '1';
-        const char* flf = getenv("MASTIC_FUSE_LAST_MISS_FC");
-        if (flf) c->k.fuse_last_miss_fc = flf[0] != '0';
-        const char* ham = getenv("MASTIC_HIT_ABSORB_MAIN");
-        if (ham) c->k.hit_absorb_main = ham[0] != '0';
-        const char* ssp = getenv("MASTIC_SMALL_SPLIT");
-        if (ssp) c->k.small_split = ssp[0] != '0';
-        const char* evw = getenv("MASTIC_EVAL_WIDE");
-        if (evw) c->k.eval_wide = evw[0] != '0';
-        const char* tnw = getenv("MASTIC_DBG_TIMING_NOWAIT");  // the round-5 last_timing bug, for its test's A/B
-        if (tnw) c->timing_nowait = tnw[0] == '1';
-        const char* ssr = getenv("MASTIC_SERIAL_SPONGES");
-        if (ssr) c->serial_sponges = ssr[0] == '1';
-        const char* lls = getenv("MASTIC_LAST_LEVEL_SEGMENTS");
-        if (lls) c->k.last_level_segments = std::max(0, atoi(lls));
-        const char* sge = getenv("MASTIC_SEG_EARLY");
-        if (sge) c->k.seg_early_payload = sge[0] != '0';
         const char* sgb = getenv("MASTIC_SEG_BALANCE");
         if (sgb) c->k.seg_balance = sgb[0] != '0';
     }
@@ -2851,7 +2798,7 @@ extern "C" int mastic_ctx_create(const mastic_params* up, mastic_ctx** out) {
     auto lds = [](const void* fn, int bytes) {
         return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
     };
-    bool attrs = lds((const void*)k_absorb_pair, 160 * 1024) && lds((const void*)k_absorb, 160 * 1024);
+    bool attrs = true;
     for (int v : LEVEL_VARIANTS)
         attrs = attrs && lds((const void*)level_kernel<F64>(v), EVAL_LDS_BYTES) &&
                 lds((const void*)level_kernel<F128>(v), EVAL_LDS_BYTES);

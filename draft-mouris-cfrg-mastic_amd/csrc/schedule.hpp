@@ -22,6 +22,8 @@ constexpr int SCHED_SPONGE_RATE = 168;  // bytes
 // ------------------------------------------------------------------ the knobs
 // The tuning fields of mastic_ctx that the schedule reads (mastic_ctx::k;
 // MASTIC_EXPERIMENT_KNOBS builds and the mastic_set_* entry points write them).
+// Every field changes the plan and tests/host/schedule_host.cpp sweeps each;
+// the knobs whose A/B is settled are constants now (DESIGN.md "Retired knobs").
 struct SchedKnobs {
     // Lanes per binder sponge.  Two (k_absorb_pair: half the dependent chain
     // per permutation, ~1.5x the VALU issue slots) while the chains are the
@@ -36,25 +38,14 @@ struct SchedKnobs {
     int absorb_mode = 0;
     size_t absorb_single_min = 65536;  // MASTIC_ABSORB_SINGLE_MIN
     int n_cus = 256;                     // compute units of the device
-    int proof_waves = SCHED_EVAL_PROOF_WAVES;  // proof waves per eval workgroup (MASTIC_PROOF_WAVES)
-    int hit_proof_waves = 0;             // ... of a fused-proof hit launch (0 = by the work split; MASTIC_HIT_PROOF_WAVES)
-    int dbg_skip = 0;                    // timing experiments only (MASTIC_DBG_SKIP; results wrong): 1 no node proofs, 2 no AES, 4 no binder sponges
     // parent ranges of the last level of a cache-less single-stream miss (plan_chunk):
-    // 0 = auto, k >= 1 forced (mastic_set_last_level_segments; MASTIC_LAST_LEVEL_SEGMENTS)
+    // 0 = auto, k >= 1 forced (mastic_set_last_level_segments)
     int last_level_segments = 0;
-    bool seg_early_payload = true;  // ... pay(L-1) on the third stream right after eval(L-1) (MASTIC_SEG_EARLY=0: with oh(L-1))
     bool seg_balance = true;        // ... ranges of equal proofs per parent (MASTIC_SEG_BALANCE=0: equal parents)
     int split_sponges = -1;  // payload sponge a level earlier, on the third stream: -1 Field128 only, 0 never, 1 always (MASTIC_SPLIT_SPONGES)
-    bool fuse_last_miss = false;    // any miss's last level with fused, overlapped node proofs (MASTIC_FUSE_LAST_MISS=1)
-    bool fuse_last_miss_fc = true;  // ... a cache-on miss's (MASTIC_FUSE_LAST_MISS_FC=0: k_node_proof)
-    bool hit_absorb_main = true;  // a single-chunk hit's sponges on the main stream (MASTIC_HIT_ABSORB_MAIN=0: sponge stream)
-    bool fc_all = false;        // A/B only: the frontier-cache kernel variant at every level (MASTIC_FC_ALL=1)
-    bool small_split = true;    // small levels' parents split into block-range items (MASTIC_SMALL_SPLIT=0: off)
-    bool eval_wide = true;      // 104-VGPR level kernel beside the 2-lane sponges (MASTIC_EVAL_WIDE=0: the 96-VGPR one)
-    int fuse_proofs = 1;        // last level's node proofs in the level kernel, overlapped with its AES: 1 on
-                                // cache hits, 2 also on cache-on misses, 0 never (MASTIC_FUSE_PROOFS; else
-                                // k_node_proof); 3 (A/B): on hits, after a workgroup barrier
-    int par_waves = 0;           // waves' worth of parents per level-kernel workgroup (0 = by field; MASTIC_PAR_WAVES)
+    // the last level's node proofs in the level kernel, overlapped with its AES,
+    // on cache hits and cache-on misses (MASTIC_FUSE_PROOFS=0: k_node_proof)
+    bool fuse_proofs = true;
 };
 
 // ------------------------------------------------------------- level geometry
@@ -130,8 +121,7 @@ inline void choose_split(int n_parents, int np_prev, int proof_waves, int nblk, 
 // ... and of a miss's fused last level: per parent also the extend pair and,
 // with no recompute, 3 + 2 nblk AES blocks; the proof waves also take level
 // L-1's node proofs first (2 np[L-1] of them, spread over level L's parents).
-inline int miss_proof_waves(const McParams& p, const SchedKnobs& k, int np_prev, int np_last, bool has_prev) {
-    if (k.hit_proof_waves > 0) return k.hit_proof_waves;
+inline int miss_proof_waves(const McParams& p, int np_prev, int np_last, bool has_prev) {
     const int epb = p.field == 64 ? 2 : 1;
     const int nblk = (p.value_len + epb - 1) / epb;
     const double proofs = 2.0 + (has_prev ? 2.0 * np_prev / std::max(1, np_last) : 0.0);
@@ -139,8 +129,7 @@ inline int miss_proof_waves(const McParams& p, const SchedKnobs& k, int np_prev,
     return std::max(1, std::min(12, (int)std::lround(SCHED_EVAL_WAVES * K / (K + A))));
 }
 
-inline int hit_proof_waves(const McParams& p, const SchedKnobs& k) {
-    if (k.hit_proof_waves > 0) return k.hit_proof_waves;
+inline int hit_proof_waves(const McParams& p) {
     const int epb = p.field == 64 ? 2 : 1;
     const int nblk = (p.value_len + epb - 1) / epb;
     const double K = 3170.0, A = (4.0 + 3.0 * nblk) * 532.0;
@@ -283,7 +272,7 @@ inline void plan_chunk(const SchedKnobs& k, const McParams& p, const TreeShape& 
     const int L = t.L, wlw = p.value_len * p.w32, groups = (n + 63) / 64;  // report groups (rows beyond n are padding)
     const std::vector<int>& np = t.n_parents;
     P.pair = k.absorb_mode == 2 || (k.absorb_mode == 0 && (size_t)n < k.absorb_single_min);
-    P.wide = P.pair && k.eval_wide;  // the level kernel may take 104 VGPRs (k_eval_aes_wide)
+    P.wide = P.pair;  // beside the 2-lane sponges the level kernel may take 104 VGPRs (k_eval_aes_wide)
     // Split schedule (single-chunk misses, MASTIC_SPLIT_SPONGES): level l's
     // payload differences are complete after eval(l), so its payload sponge
     // starts then, on the third stream, while its one-hot sponge still waits
@@ -296,25 +285,20 @@ inline void plan_chunk(const SchedKnobs& k, const McParams& p, const TreeShape& 
     const bool split_on = k.split_sponges < 0 ? p.field == 128 : k.split_sponges > 0;
     P.split = split_on && !hit && !pipelined;
     // the last level's node proofs in the level kernel (after each workgroup's
-    // parents) instead of a k_node_proof launch: cache hits, and with
-    // MASTIC_FUSE_PROOFS=2 cache-on misses too (whole parents only)
-    // A miss's last level is fused too when the frontier cache is on (the
-    // sweeps: c2sweep +1 %, its level kernels -4 %), not without it (C2 -1.7 %,
-    // C5 -0.9 %: the FC kernel's 128 VGPRs leave no room for the previous
-    // level's sponge waves beside it; profiles/r04_v21_ab_fused_last_miss.txt)
-    P.fuse_last = hit ? k.fuse_proofs >= 1
-                      : ((cache && (k.fuse_proofs == 2 || (k.fuse_proofs >= 1 && k.fuse_last_miss_fc))) ||
-                         (k.fuse_last_miss && k.fuse_proofs >= 1));
+    // parents) instead of a k_node_proof launch: cache hits, and a miss's
+    // when the frontier cache is on (the sweeps: c2sweep +1 %, its level
+    // kernels -4 %), not without it (C2 -1.7 %, C5 -0.9 %: the FC kernel's
+    // 128 VGPRs leave no room for the previous level's sponge waves beside
+    // it; profiles/r04_v21_ab_fused_last_miss.txt)
+    P.fuse_last = k.fuse_proofs && (hit || cache);
     // The last level's sponges: on the main stream for a hit that runs as one
     // chunk (nothing to overlap them with: the next work on the main stream
     // needs them; the cross-stream event round trip cost ~0.08 ms per call),
     // else on the sponge stream after the level's earlier sponges.
-    P.last_stream = (hit && !pipelined && k.hit_absorb_main) ? ST_MAIN : ST_SPONGE;
+    P.last_stream = (hit && !pipelined) ? ST_MAIN : ST_SPONGE;
     // items per workgroup: par_waves x ppw, par_waves = the AES waves (the
-    // proof waves mop up after their proofs).  MASTIC_PAR_WAVES=16 hands
-    // all waves parents from the start: measured neutral on C4 and C2 and
-    // 3 % slower on C5 (profiles/r02_v12_ab_level_kernel.json)
-    const int par_waves = k.par_waves > 0 ? k.par_waves : SCHED_EVAL_WAVES - k.proof_waves;
+    // proof waves mop up after their proofs)
+    const int par_waves = SCHED_EVAL_WAVES - SCHED_EVAL_PROOF_WAVES;
     // Segmented last level (mastic_set_last_level_segments): a miss with no
     // frontier cache, not pipelined, beside the 2-lane sponges.  Level L's
     // parents (BFS order, as are both binder messages) are cut into nseg
@@ -333,7 +317,7 @@ inline void plan_chunk(const SchedKnobs& k, const McParams& p, const TreeShape& 
     // is complete after eval(L-1), so it goes to the third stream at once
     // (after absorb(L-2), which holds the payload sponge's previous piece)
     // instead of waiting, paired with oh(L-1), for eval(L)'s first proofs.
-    P.seg_early = P.nseg > 1 && k.seg_early_payload && !P.split && L >= 2;
+    P.seg_early = P.nseg > 1 && !P.split && L >= 2;
     const std::vector<int> seg_beg = segment_ranges(k, t, P.nseg);
     // a hit's levels 0..L-1 are cached: nothing is planned for them
     for (int lv = 0; hit && lv < L; lv++) {
@@ -367,14 +351,14 @@ inline void plan_chunk(const SchedKnobs& k, const McParams& p, const TreeShape& 
         // (<= 32 parents: their pass-0 flags live in the workgroup's sync words)
         a.split = 1;
         a.split_blocks = nblk;
-        if (!hit && l < L && k.small_split && np[l] <= 32 && !(k.dbg_skip & 2))
-            choose_split(np[l], l > 0 ? np[l - 1] : 0, k.proof_waves, nblk, &a.split, &a.split_blocks);
+        if (!hit && l < L && np[l] <= 32)
+            choose_split(np[l], l > 0 ? np[l - 1] : 0, SCHED_EVAL_PROOF_WAVES, nblk, &a.split, &a.split_blocks);
         const bool fuse = P.fuse_last && l == L;
-        a.fuse_proofs = fuse ? (k.fuse_proofs == 3 ? 3 : 1) : 0;
-        a.aes_waves = SCHED_EVAL_WAVES - k.proof_waves;
-        if (fuse && a.fuse_proofs == 1)
-            a.aes_waves = SCHED_EVAL_WAVES - (hit ? hit_proof_waves(p, k)
-                                                  : miss_proof_waves(p, k, np[l - 1 < 0 ? 0 : l - 1], np[l], l > 0));
+        a.fuse_proofs = fuse ? 1 : 0;
+        a.aes_waves = SCHED_EVAL_WAVES - SCHED_EVAL_PROOF_WAVES;
+        if (fuse)
+            a.aes_waves = SCHED_EVAL_WAVES -
+                          (hit ? hit_proof_waves(p) : miss_proof_waves(p, np[l - 1 < 0 ? 0 : l - 1], np[l], l > 0));
         a.par_waves = par_waves;
         // the frontier-cache variant only where its features are used: the
         // last level (convert seeds staged for the cache) and a hit (parent
@@ -382,7 +366,7 @@ inline void plan_chunk(const SchedKnobs& k, const McParams& p, const TreeShape& 
         // plain kernel (the variant's uniform branches and extra spills cost
         // a few per cent).  Beside the 2-lane sponges (96 VGPRs) the plain
         // variants take 104 (k_eval_aes_wide); beside k_absorb (128) they keep 96
-        a.variant = ((cache && (hit || l == L || k.fc_all)) || fuse)
+        a.variant = ((cache && (hit || l == L)) || fuse)
                         ? LV_GEN | LV_FC
                         : (P.wide ? LV_WIDE : 0) | (a.split > 1 ? LV_SPLIT : 0) | (l == 0 || l == L ? LV_GEN : 0);
         const int nq = l == L ? P.nseg : 1;  // the segmented last level: one launch per parent range

@@ -6,7 +6,10 @@
 //       (WANT_GRID below), and the rows the move's issue listed, one by one;
 //   (b) plan_chunk over a grid of trees, fields, modes and knobs: every plan
 //       covers each level, proof and sponge byte exactly once, in an order
-//       the streams and waits enforce.
+//       the streams and waits enforce.  The grid spans the whole knob space:
+//       every SchedKnobs field that can change a plan is swept
+//       (last_level_segments, split_sponges, fuse_proofs, absorb_mode,
+//       seg_balance; absorb_single_min through n on either side of it).
 // Prints "schedule_host: OK" and returns 0, or one line per failure and 1.
 // Run under ASan/UBSan by tests/test_schedule_host.py.
 #include <cstdio>
@@ -52,11 +55,11 @@ static std::vector<long> helper_grid() {
     std::vector<long> g;
     SchedKnobs K;
     for (int field : {64, 128})
-        for (int vl : {1, 2, 3, 5, 9, 18, 33, 64}) g.push_back(hit_proof_waves(params(field, vl), K));
+        for (int vl : {1, 2, 3, 5, 9, 18, 33, 64}) g.push_back(hit_proof_waves(params(field, vl)));
     const int prevs[5][3] = {{0, 1, 0}, {64, 128, 1}, {5000, 10000, 1}, {1, 2, 1}, {100, 101, 1}};
     for (int field : {64, 128})
         for (int vl : {1, 2, 18, 64})
-            for (const int* q : prevs) g.push_back(miss_proof_waves(params(field, vl), K, q[0], q[1], q[2] != 0));
+            for (const int* q : prevs) g.push_back(miss_proof_waves(params(field, vl), q[0], q[1], q[2] != 0));
     for (int np : {1, 2, 3, 5, 8, 16, 17, 32})
         for (int nblk : {1, 2, 3, 9, 17, 64}) {
             int split = 0, blocks = 0;
@@ -115,12 +118,12 @@ static void check_helpers() {
         CHECK(g[i] == WANT_GRID[i], "grid value %zu is %ld, recorded %ld", i, g[i], WANT_GRID[i]);
     // the rows listed when the helpers moved
     SchedKnobs K;
-    CHECK(hit_proof_waves(params(64, 2), K) == 7, "-");
-    CHECK(hit_proof_waves(params(64, 18), K) == 3, "-");
-    CHECK(hit_proof_waves(params(128, 64), K) == 1, "-");
-    CHECK(miss_proof_waves(params(64, 18), K, 5000, 10000, true) == 5, "-");
-    CHECK(miss_proof_waves(params(64, 2), K, 64, 128, true) == 10, "-");
-    CHECK(miss_proof_waves(params(64, 2), K, 0, 1, false) == 8, "-");
+    CHECK(hit_proof_waves(params(64, 2)) == 7, "-");
+    CHECK(hit_proof_waves(params(64, 18)) == 3, "-");
+    CHECK(hit_proof_waves(params(128, 64)) == 1, "-");
+    CHECK(miss_proof_waves(params(64, 18), 5000, 10000, true) == 5, "-");
+    CHECK(miss_proof_waves(params(64, 2), 64, 128, true) == 10, "-");
+    CHECK(miss_proof_waves(params(64, 2), 0, 1, false) == 8, "-");
     const int splits[][4] = {{1, 9, 9, 1},   {1, 64, 16, 4}, {2, 9, 5, 2},  {2, 64, 7, 10}, {16, 64, 8, 8},
                              {32, 64, 4, 16}, {32, 9, 3, 3},  {1, 1, 1, 1}, {7, 1, 1, 1},   {32, 1, 1, 1}};
     for (const int* r : splits) {
@@ -185,7 +188,7 @@ static void check_plan(const Case& c) {
             next = a.p0 + a.cnt;
             if (a.level >= lo && a.level <= L) made[a.level].resize(std::max(0, std::min(next, np[a.level])), j);
             CHECK(legal_variant(a.variant), "%s: launch %d variant %d", nm, j, a.variant);
-            const bool fc = (c.cache && (c.hit || a.level == L || c.K.fc_all)) || a.fuse_proofs > 0;
+            const bool fc = (c.cache && (c.hit || a.level == L)) || a.fuse_proofs > 0;
             CHECK(((a.variant & LV_FC) != 0) == fc, "%s: launch %d FC", nm, j);
             if (!fc) {
                 CHECK(((a.variant & LV_WIDE) != 0) == P.wide, "%s: launch %d WIDE", nm, j);
@@ -302,7 +305,7 @@ static void check_plan(const Case& c) {
     CHECK(P.nseg >= 1 && P.nseg <= np[L] && (P.nseg == 1 || (!c.hit && !c.cache && !c.pipelined && P.pair && !P.fuse_last)),
           "%s: %d segments", nm, P.nseg);
     CHECK(!P.split || (!c.hit && !c.pipelined), "%s: split", nm);
-    CHECK(P.wide == (P.pair && c.K.eval_wide), "%s: wide", nm);
+    CHECK(P.wide == P.pair, "%s: wide", nm);
 }
 
 static int check_plans() {
@@ -317,29 +320,34 @@ static int check_plans() {
                     for (int pipelined = 0; pipelined < 2; pipelined++)
                         for (int segs : {0, 1, 3, 1000})
                             for (int split : {-1, 0, 1})
-                                for (int fuse : {0, 1, 2})
-                                    for (int n : {70, 100000})
-                                        for (int wc = 0; wc < 2; wc++) {
-                                            if (mode == 2 && (L == 0 || wc)) continue;  // no hit at level 0 or with the FLP
-                                            Case c;
-                                            c.K.last_level_segments = segs;
-                                            c.K.split_sponges = split;
-                                            c.K.fuse_proofs = fuse;
-                                            c.p = params(field, field == 64 ? 2 : 18);
-                                            c.t = tree_of(np);
-                                            c.t.weight_check = wc != 0;
-                                            c.n = n;
-                                            c.hit = mode == 2;
-                                            c.cache = mode >= 1;
-                                            c.pipelined = pipelined != 0;
-                                            char buf[160];
-                                            snprintf(buf, sizeof buf, "L%d big%d F%d mode%d pipe%d seg%d split%d fuse%d n%d wc%d", L,
-                                                     big, field, mode, pipelined, segs, split, fuse, n, wc);
-                                            c.name = buf;
-                                            check_plan(c);
-                                            n_plans++;
-                                            if (g_failures) return n_plans;
-                                        }
+                                for (int fuse : {0, 1})
+                                    for (int absorb : {0, 1, 2})
+                                        for (int balance : {0, 1})
+                                            for (int n : {70, 100000})
+                                                for (int wc = 0; wc < 2; wc++) {
+                                                    if (mode == 2 && (L == 0 || wc)) continue;  // no hit at level 0 or with the FLP
+                                                    Case c;
+                                                    c.K.last_level_segments = segs;
+                                                    c.K.split_sponges = split;
+                                                    c.K.fuse_proofs = fuse != 0;
+                                                    c.K.absorb_mode = absorb;
+                                                    c.K.seg_balance = balance != 0;
+                                                    c.p = params(field, field == 64 ? 2 : 18);
+                                                    c.t = tree_of(np);
+                                                    c.t.weight_check = wc != 0;
+                                                    c.n = n;
+                                                    c.hit = mode == 2;
+                                                    c.cache = mode >= 1;
+                                                    c.pipelined = pipelined != 0;
+                                                    char buf[200];
+                                                    snprintf(buf, sizeof buf,
+                                                             "L%d big%d F%d mode%d pipe%d seg%d split%d fuse%d abs%d bal%d n%d wc%d", L,
+                                                             big, field, mode, pipelined, segs, split, fuse, absorb, balance, n, wc);
+                                                    c.name = buf;
+                                                    check_plan(c);
+                                                    n_plans++;
+                                                    if (g_failures) return n_plans;
+                                                }
         }
     return n_plans;
 }

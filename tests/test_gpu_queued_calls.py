@@ -168,8 +168,8 @@ def test_hit_timing_with_busy_sponge_stream(mastic_amd):
     test hook: a 400 ms idle kernel queued there first), mastic_last_timing3
     right after the call -- no synchronize -- must wait for the marks
     themselves and return finite times (round 5's "device not ready" failure
-    in a 4-rank run sharing one GPU; fixed in 47221e6).  The knob build's
-    MASTIC_DBG_TIMING_NOWAIT=1 restores the old behaviour: tools/timing_fix_ab.py."""
+    in a 4-rank run sharing one GPU; fixed in 47221e6; the A/B against the
+    old behaviour is on record in profiles/r06_v3_timing_fix_ab.txt)."""
     rng = random.Random(95)
     m = mastic_amd.MasticCount(8)
     n = 128

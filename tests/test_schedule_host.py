@@ -3,7 +3,8 @@ helpers and plan_chunk, which mastic_hip.hip struct Chunk executes), on the host
 under ASan/UBSan.  tests/host/schedule_host.cpp checks that the helpers return
 the values recorded before they moved out of mastic_hip.hip, and that every
 plan over a grid of tree depths and widths, both fields, hit / miss, cache
-on / off, pipelined or not, forced segments, split sponges and fuse_proofs
+on / off, pipelined or not, and every SchedKnobs field that changes a plan
+(forced segments, split sponges, fuse_proofs, absorb_mode, seg_balance)
 covers each level, node proof and sponge byte exactly once, in an order that
 its streams and waits enforce, with legal kernel variants and the event
 counts it declares.  The GPU side runs the same plans in the prep_init tests

@@ -29,7 +29,7 @@ for s in "$@"; do
     cfg=${rest%%:*}; args=${rest#*:}; [ "$args" = "$rest" ] && args=""
     args=${args//+/ }; cfg=${cfg:-c2}
     case $kind in
-        tests) step tests 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread --durations=15 ;;
+        tests) step tests 1100 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread --durations=15 ;;
         ptest) step "ptest_$(basename "$cfg" .py)" 600 python -u -m pytest "$cfg" -m gpu -x -v --timeout 120 --timeout-method thread ;;
         smoke) step smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
         bench) tag=$(echo "$args" | tr -cd 'a-z0-9'); step "bench_${cfg}${tag:+_$tag}" 900 python3 -u bench.py --full --config "$cfg" $args ;;
