@@ -23,6 +23,7 @@
 #pragma once
 #include "aes.hpp"
 #include "flp.hpp"
+#include "group_fold.hpp"
 #include "keccak.hpp"
 
 // ------------------------------------------------------------- prefix states
@@ -1825,6 +1826,64 @@ __global__ __launch_bounds__(256) void k_fold(const uint32_t* out, int n, int st
     if (threadIdx.x == 0) {
         E x = red[0];
         for (int i = 0; i < F::W32; i++) agg_words[(size_t)row * F::W32 + i] = F::word(x, i);
+    }
+}
+
+// agg[g][i] = sum over the valid reports of group g of out[i]: the fold of
+// mastic_aggregate_grouped (plan, accumulation scheme and why: group_fold.hpp).
+// Workgroup (row, y) streams reports [y * chunk, (y + 1) * chunk) of one output
+// element as k_fold does and adds each element's 32-bit words into the 64-bit
+// LDS counters of its group, cnt[(g * W32 + word) * copies + copy]; groups
+// outside [g0, g0 + gpp) (another pass, MASTIC_GROUP_NONE, a masked report)
+// add nothing.  Then one lane per group sums the copies, recombines the words
+// mod p and stores part[y][g][row] (gridDim.y == 1: the pass's slice of the
+// result itself).
+template <class F>
+__global__ __launch_bounds__(256) void k_fold_grouped(const uint32_t* out, int n, int stride, const uint32_t* group,
+                                                      const uint8_t* valid, int chunk, uint32_t g0, int gpp,
+                                                      int copies, uint32_t* part) {
+    typedef typename F::E E;
+    extern __shared__ unsigned long long gf_cnt[];
+    const int slots = gpp * F::W32 * copies;
+    for (int i = (int)threadIdx.x; i < slots; i += 256) gf_cnt[i] = 0;
+    __syncthreads();
+    const int row = blockIdx.x;
+    const int r0 = blockIdx.y * chunk;
+    const int r1 = min(n, r0 + chunk);
+    const uint32_t cp = threadIdx.x & (uint32_t)(copies - 1);
+    auto gid = [&](int r) {
+        const uint32_t g = group[r];
+        return (valid && !valid[r]) ? 0xFFFFFFFFu : g - g0;  // MASTIC_GROUP_NONE - g0 >= gpp as well
+    };
+    auto put = [&](uint32_t g, E x) {
+        if (g >= (uint32_t)gpp) return;
+#pragma unroll
+        for (int i = 0; i < F::W32; i++)
+            atomicAdd(&gf_cnt[(g * F::W32 + i) * copies + cp], (unsigned long long)F::word(x, i));
+    };
+    int r = r0 + (int)threadIdx.x;
+    for (; r + 768 < r1; r += 1024) {
+        const E x0 = pl_load<F>(out, row, stride, r), x1 = pl_load<F>(out, row, stride, r + 256),
+                x2 = pl_load<F>(out, row, stride, r + 512), x3 = pl_load<F>(out, row, stride, r + 768);
+        const uint32_t i0 = gid(r), i1 = gid(r + 256), i2 = gid(r + 512), i3 = gid(r + 768);
+        put(i0, x0);
+        put(i1, x1);
+        put(i2, x2);
+        put(i3, x3);
+    }
+    for (; r < r1; r += 256) put(gid(r), pl_load<F>(out, row, stride, r));
+    __syncthreads();
+    part += (size_t)blockIdx.y * gpp * gridDim.x * F::W32;
+    for (int g = (int)threadIdx.x; g < gpp; g += 256) {
+        uint64_t s[F::W32];
+#pragma unroll
+        for (int i = 0; i < F::W32; i++) {
+            s[i] = 0;
+            for (int c = 0; c < copies; c++) s[i] += gf_cnt[(g * F::W32 + i) * copies + c];
+        }
+        const E x = limbs_to_elem<F>(s);
+#pragma unroll
+        for (int i = 0; i < F::W32; i++) part[((size_t)g * gridDim.x + row) * F::W32 + i] = F::word(x, i);
     }
 }
 

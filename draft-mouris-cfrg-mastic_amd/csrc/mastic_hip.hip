@@ -212,6 +212,7 @@ struct mastic_ctx {
     DevBuf consts;   // alpha^-i table for prove
     DevBuf agg_valid, agg_out;  // mastic_aggregate staging
     DevBuf agg_part;            // per-chunk partial sums of a split fold (aggregate_impl)
+    DevBuf grp_ids, grp_part, grp_out;  // mastic_aggregate_grouped: group ids, per-chunk partials, output staging
     DevBuf stage;               // result encoding / decide staging
     SchedKnobs k;               // the knobs the launch plan reads (schedule.hpp)
     ChunkPlan plans[2];         // the last prep_init's plans (full chunk, last chunk): their vectors are reused
@@ -1547,6 +1548,80 @@ extern "C" int mastic_aggregate_device_on_stream(mastic_ctx* c, int agg_id, cons
     int rc = aggregate_impl(c, agg_id, valid, (uint32_t*)dev_agg_share);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's stream (e.g. RCCL's) reads it next
+    return 0;
+}
+
+// One agg share per batch bucket in one pass over the out shares.  Every
+// decision (the id check, passes, copies, chunks, sizes) is group_fold.hpp's.
+extern "C" int mastic_aggregate_grouped(mastic_ctx* c, int agg_id, const uint32_t* group, size_t n_groups,
+                                        const uint8_t* valid, uint8_t* agg_shares, uint64_t* counts) {
+    DeviceScope ds_(c);
+    if (!c || (agg_id != 0 && agg_id != 1)) return fail(c, MASTIC_EINVAL, "invalid aggregator ID");
+    Result& R = c->res[agg_id];
+    if (!R.ready) return fail(c, MASTIC_EINVAL, "no prep_init result for this aggregator");
+    const McParams& p = c->p;
+    const size_t n = R.n;
+    const size_t rows = (size_t)R.n_prefixes * (1 + p.output_len);
+    if (n_groups == 0 || n_groups > MASTIC_MAX_GROUPS)
+        return fail(c, MASTIC_EINVAL, "n_groups must be 1 .. %d", MASTIC_MAX_GROUPS);
+    if (n_groups * rows > (size_t)INT_MAX) return fail(c, MASTIC_EINVAL, "n_groups * rows exceeds INT_MAX");
+    if (n && !group) return fail(c, MASTIC_EINVAL, "null group ids");
+    if (rows && !agg_shares) return fail(c, MASTIC_EINVAL, "null agg shares buffer");
+    std::vector<uint64_t> cnt(n_groups);
+    const long long bad = check_groups(group, n, n_groups, valid, cnt.data());
+    if (bad >= 0)
+        return fail(c, MASTIC_EINVAL, "report %lld: group id %u is not below n_groups = %zu", bad, group[bad], n_groups);
+    const GroupFoldPlan pl = plan_group_fold(p.w32, n, rows, n_groups, c->k.n_cus, 0, 0);
+    const size_t out_bytes = n_groups * rows * p.w32 * 4;
+    if (rows) {
+        // all device memory first (each allocation takes the fail_allocs hook):
+        // nothing is launched before the last of them succeeded
+        auto alloc = [&](DevBuf& b, size_t bytes) { return !c->inject_alloc_failure() && b.grow(bytes); };
+        if ((n && !alloc(c->grp_ids, n * 4)) || (n && valid && !alloc(c->agg_valid, n)) ||
+            (pl.partial_bytes && !alloc(c->grp_part, pl.partial_bytes)) || !alloc(c->grp_out, out_bytes))
+            return fail(c, MASTIC_ENOMEM, "out of device memory (grouped fold)");
+        uint32_t* stage = c->grp_out.as<uint32_t>();
+        if (pl.chunks == 0) {
+            HIPCHK(c, hipMemsetAsync(stage, 0, out_bytes, c->stream));
+        } else {
+            const uint8_t* dv = nullptr;
+            HIPCHK(c, hipMemcpyAsync(c->grp_ids.p, group, n * 4, hipMemcpyHostToDevice, c->stream));
+            if (valid) {
+                HIPCHK(c, hipMemcpyAsync(c->agg_valid.p, valid, n, hipMemcpyHostToDevice, c->stream));
+                dv = c->agg_valid.as<uint8_t>();
+            }
+            const dim3 grid(pl.grid_x, pl.grid_y);
+            for (uint32_t k = 0; k < pl.passes; k++) {
+                const uint32_t g0 = k * pl.groups_per_pass;
+                const uint32_t gpp = std::min<uint32_t>(pl.groups_per_pass, (uint32_t)n_groups - g0);
+                uint32_t* dst = stage + (size_t)g0 * rows * p.w32;
+                uint32_t* part = pl.chunks > 1 ? c->grp_part.as<uint32_t>() : dst;
+                if (p.field == 64)
+                    hipLaunchKernelGGL(k_fold_grouped<F64>, grid, dim3(256), pl.lds_bytes, c->stream,
+                                       R.out.as<uint32_t>(), (int)n, (int)R.stride, c->grp_ids.as<uint32_t>(), dv,
+                                       (int)pl.chunk, g0, (int)gpp, (int)pl.copies, part);
+                else
+                    hipLaunchKernelGGL(k_fold_grouped<F128>, grid, dim3(256), pl.lds_bytes, c->stream,
+                                       R.out.as<uint32_t>(), (int)n, (int)R.stride, c->grp_ids.as<uint32_t>(), dv,
+                                       (int)pl.chunk, g0, (int)gpp, (int)pl.copies, part);
+                HIPCHK(c, hipGetLastError());
+                if (pl.chunks > 1) {
+                    const size_t ne = (size_t)gpp * rows;
+                    const dim3 g2((unsigned)((ne + 255) / 256));
+                    if (p.field == 64)
+                        hipLaunchKernelGGL(k_fold_shares<F64>, g2, dim3(256), 0, c->stream, (const uint32_t*)part,
+                                           (int)pl.chunks, (int)ne, dst);
+                    else
+                        hipLaunchKernelGGL(k_fold_shares<F128>, g2, dim3(256), 0, c->stream, (const uint32_t*)part,
+                                           (int)pl.chunks, (int)ne, dst);
+                    HIPCHK(c, hipGetLastError());
+                }
+            }
+        }
+        HIPCHK(c, hipMemcpyAsync(agg_shares, stage, out_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    if (counts) std::copy(cnt.begin(), cnt.end(), counts);
     return 0;
 }
 

@@ -41,7 +41,7 @@ EXPORTS = [
     "mastic_allgather_fold", "mastic_aggregate_merged", "mastic_merge_host",
     "mastic_nonce_set_create", "mastic_nonce_set_destroy", "mastic_nonce_set_count", "mastic_nonce_set_admit",
     "mastic_nonce_set_admit_reports", "mastic_nonce_set_contains", "mastic_nonce_set_export",
-    "mastic_reports_compact",
+    "mastic_reports_compact", "mastic_aggregate_grouped",
 ]
 COMM_ID_BYTES = 128  # MASTIC_COMM_ID_BYTES (= RCCL's NCCL_UNIQUE_ID_BYTES)
 ROCM_PATH = "/opt/rocm"  # the image's ROCm (the library dlopens librccl.so.1 from its lib/ on first comm use)
@@ -143,6 +143,7 @@ def lib():
                     "mastic_prep_init": (i32, [P, P, u8p, sz, u8p, sz, i32, u8p, sz]),
                     "mastic_prep_result": (i32, [P, i32, P, P, P, P]),
                     "mastic_aggregate": (i32, [P, i32, P, P]),
+                    "mastic_aggregate_grouped": (i32, [P, i32, P, sz, P, P, P]),
                     "mastic_synchronize": (i32, [P]),
                     "mastic_prep_init_batch": (i32, [P, u8p, sz, u8p, sz, i32, u8p, sz, sz, P, P, P, P, P, P, P]),
                     "mastic_decide_batch": (i32, [P, u8p, sz, u8p, sz, sz, P, P, P, P]),

@@ -21,6 +21,8 @@ PROOF_SIZE = 32
 STATUS_OK = 0
 STATUS_QUERY_ABORT = -2    # FlpBBCGGI19.query: the test point is a root of unity
 STATUS_NONCANONICAL = -3   # a wire field element (payload correction word, leader proof share) is >= p
+NO_GROUP = 0xFFFFFFFF      # MASTIC_GROUP_NONE: a report of aggregate_grouped that belongs to no bucket
+MAX_GROUPS = 65536         # MASTIC_MAX_GROUPS
 CIRCUIT_IDS = {"Count": 1, "Sum": 2, "SumVec": 3, "Histogram": 4, "MultihotCountVec": 5}
 
 
@@ -107,6 +109,7 @@ class Mastic:
         self.max_measurement = max_measurement
         self.chunk_length = chunk_length
         self.vidpf = VidpfInfo(self.field, bits, sz.value_len)
+        self._batch_n = [None, None]  # reports of each aggregator's last prep_init (aggregate_grouped's length check)
         if circuit == "Sum":
             self._wbits = max_measurement.bit_length()
             self._offset = 2 ** self._wbits - 1 - max_measurement
@@ -210,6 +213,7 @@ class Mastic:
             self._ctx, verify_key, len(verify_key), ctx, len(ctx), agg_id, enc, len(enc), n, _lib.buf(nonces),
             _lib.buf(public_shares), _lib.buf(input_shares), _lib.buf(ps), _lib.buf(js), _lib.buf(out),
             _lib.buf(st)))
+        self._batch_n[agg_id] = n
         return (ps.tobytes(), js.tobytes(), None if out is None else out.tobytes(), st)
 
     def decide_batch(self, ctx: bytes, agg_param, prep_shares_0: bytes, prep_shares_1: bytes):
@@ -325,6 +329,36 @@ class Mastic:
         _check(self._ctx, _lib.lib().mastic_aggregate(self._ctx, agg_id, _lib.buf(v), _lib.buf(out)))
         return out.tobytes() if raw else self.field.decode_vec(out.tobytes())
 
+    def aggregate_grouped(self, agg_id: int, agg_param, groups, n_groups: int, valid=None, raw=False):
+        """``mastic_aggregate_grouped``: the out shares of the last
+        prep_init(_batch) of agg_id folded into one agg share per batch bucket,
+        in one pass over the out shares.  ``groups[r]`` is report r's bucket
+        (0 .. n_groups-1) or :data:`NO_GROUP`; ``valid`` masks reports as in
+        :meth:`aggregate_device`.  Returns ``(shares, counts)``: ``shares`` is
+        the list of the n_groups agg shares (bytes if ``raw``, else decoded
+        field vectors), ``counts`` the uint64 array of reports folded into
+        each (the buckets' ``num_measurements``)."""
+        enc = self.encode_agg_param(agg_param) if not isinstance(agg_param, (bytes, bytearray)) else bytes(agg_param)
+        (_level, count, _wc) = self._agg_param_header(enc)
+        g = np.ascontiguousarray(np.asarray(groups, dtype=np.uint32))
+        v = None if valid is None else np.ascontiguousarray(np.asarray(valid, dtype=np.uint8))
+        share = count * (1 + self.OUTPUT_LEN) * self.field.ENCODED_SIZE
+        n_groups = int(n_groups)
+        if not 1 <= n_groups <= MAX_GROUPS:
+            raise ValueError("n_groups must be 1 .. %d" % MAX_GROUPS)
+        n = self._batch_n[agg_id] if agg_id in (0, 1) else None  # None: the library refuses the call
+        if g.ndim != 1 or (n is not None and g.size != n):
+            raise ValueError("groups has %d entries, the batch has %s reports" % (g.size, n))
+        if v is not None and v.size != g.size:
+            raise ValueError("valid has %d entries, groups has %d" % (v.size, g.size))
+        out = np.empty(n_groups * share, np.uint8)
+        counts = np.zeros(n_groups, np.uint64)
+        _check(self._ctx, _lib.lib().mastic_aggregate_grouped(self._ctx, agg_id, _lib.buf(g), n_groups, _lib.buf(v),
+                                                              _lib.buf(out), _lib.buf(counts)))
+        data = out.tobytes()
+        shares = [data[i * share:(i + 1) * share] for i in range(n_groups)]
+        return (shares if raw else [self.field.decode_vec(s) for s in shares], counts)
+
     # ------------------------------------------- device-resident batches
     def reports_shard(self, ctx: bytes, alphas_packed: bytes, betas: bytes, nonces: bytes, rands: bytes):
         """Shard n reports on the GPU and keep them resident in HBM."""
@@ -347,6 +381,7 @@ class Mastic:
         self._check_verify_key(verify_key)
         _check(self._ctx, _lib.lib().mastic_prep_init(self._ctx, reports._ptr, verify_key, len(verify_key), ctx,
                                                       len(ctx), agg_id, enc, len(enc)))
+        self._batch_n[agg_id] = reports.n
 
     def prep_result(self, reports, agg_id: int, agg_param, want_out_shares=False):
         """Wire results of the last prep_init_device for agg_id:

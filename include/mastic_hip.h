@@ -260,6 +260,40 @@ int mastic_aggregate(mastic_ctx* ctx, int agg_id, const uint8_t* valid, uint8_t*
  * Returns when the buffer is written. */
 int mastic_aggregate_device_on_stream(mastic_ctx* ctx, int agg_id, const uint8_t* valid, void* dev_agg_share,
                                       void* caller_stream);
+/* Grouped fold (additive, ABI 8): the out shares of the last prep_init for
+ * agg_id folded into one agg share per batch bucket, reading the out shares
+ * once (agg_update, mastic.py:384-388, routed per report).  group[r] (n
+ * entries, n = that prep_init's reports) is report r's bucket, 0 .. n_groups-1,
+ * or MASTIC_GROUP_NONE for a report that belongs to no bucket.
+ * agg_shares[g] (n_groups x rows x field_bytes, group-major,
+ * rows = len(prefixes)*(1+output_len)) = the sum mod p of out[r] over the
+ * reports with group[r] == g and (valid == NULL or valid[r] != 0); each
+ * group's share is contiguous and laid out exactly as the output of
+ * mastic_aggregate (encode_vec), so it goes straight to unshard or
+ * mastic_merge_host; an empty group is agg_init's zeros.  counts[g] (n_groups,
+ * may be NULL) = the reports folded into g (the bucket's num_measurements).
+ * With n_groups == 1 and every report in group 0 the output is byte-identical
+ * to that of mastic_aggregate.
+ * MASTIC_EINVAL, with nothing launched and nothing written: an id >= n_groups
+ * other than MASTIC_GROUP_NONE (the message names the first such report),
+ * n_groups == 0 or > MASTIC_MAX_GROUPS, n_groups * rows > INT_MAX, a NULL
+ * group with n > 0, a NULL agg_shares with rows > 0, a bad agg_id, no
+ * prep_init result.  n == 0 writes zeros, rows == 0 writes no share (both
+ * succeed).  The call blocks; its work runs on the ctx's main stream, after
+ * the prep_init that produced the result.  Every device allocation (group
+ * ids, mask, per-chunk partials, output staging) is made before any launch;
+ * after MASTIC_ENOMEM the prep result is untouched and the call may be
+ * repeated.  Beside the output staging the extra device memory is bounded:
+ * the partials obey a 64 MiB cap, raised to what a single report chunk needs.
+ * More than 4,096 (Field64) / 2,048 (Field128) groups are folded in several
+ * passes, each of which reads the out shares again.
+ * Multi-rank: a grouped result is a vector of n_groups * rows field elements;
+ * mastic_merge_host / mastic_allgather_fold merge it across ranks as they do
+ * a single share (n_elems = n_groups * rows), and the counts add up. */
+#define MASTIC_GROUP_NONE 0xFFFFFFFFu
+#define MASTIC_MAX_GROUPS 65536
+int mastic_aggregate_grouped(mastic_ctx* ctx, int agg_id, const uint32_t* group, size_t n_groups,
+                             const uint8_t* valid, uint8_t* agg_shares, uint64_t* counts);
 /* Multi-GPU merge (Mastic.merge, mastic.py:390-397) of n_shares agg shares
  * of n_elems elements each, all in DEVICE memory of the ctx's GPU (e.g. the
  * output of an RCCL all-gather): dev_out[e] = sum_s dev_shares[s][e] mod p.
