@@ -20,8 +20,9 @@ nonce or seed in report 3 only: wave 0 has one lane that consumes one
 candidate more than the rest, wave 1 has none.
 
 A real Field128 rejection (probability 2^-59 per candidate) cannot be found by
-search, and there is no hook that fakes one: Field128's sampler is covered for
-acceptance only.
+search; tests/test_gpu_xof_ops.py (part C) runs sponge_squeeze_vec from chosen
+sponge states instead, whose first block holds rejected candidates at every
+position for both fields.
 """
 import functools
 import json
