@@ -1,8 +1,9 @@
-// The host side of mastic_aggregate_grouped (C++17; no HIP): the check of the
-// group ids, the launch plan of k_fold_grouped (kernels.hpp) and the exact
-// recombination of its integer word sums into a field element.  mastic_hip.hip
-// executes the plan and decides nothing itself; tests/host/group_fold_host.cpp
-// checks all three on the host.
+// The host side of the folds (C++17; no HIP): for mastic_aggregate_grouped the
+// check of the group ids, the launch plan of k_fold_grouped (kernels.hpp) and
+// the exact recombination of its integer word sums into a field element; for
+// the ungrouped fold the chunking of k_fold (plan_fold).  fold.hpp executes
+// the plans and decides nothing itself; tests/host/group_fold_host.cpp checks
+// all of it on the host.
 //
 // The fold.  The out shares are word planes out[row][word][stride]; a
 // workgroup (row, chunk) streams the reports of its chunk exactly as k_fold
@@ -97,6 +98,28 @@ inline long long check_groups(const uint32_t* group, size_t n, size_t n_groups, 
     return -1;
 }
 
+// The ungrouped fold (k_fold, one running sum per row): few rows over many
+// reports (a sweep level: ~700 rows x 1M reports) are split into chunks of
+// reports so the grid (rows, chunks) fills the chip, and k_fold_shares merges
+// the chunks' partial sums mod p.
+struct FoldPlan {
+    size_t chunks = 1;         // report chunks (grid y); an empty batch still writes its all-zero agg share: one chunk
+    size_t chunk = 1;          // reports per chunk; a multiple of 256 when chunks > 1
+    size_t partial_bytes = 0;  // [chunks][rows] elements, at least 1 MiB; 0 with one chunk (written in place)
+};
+
+// w32: 32-bit words per element (2 / 4).  rows >= 1 (no rows: nothing is launched).
+inline FoldPlan plan_fold(int w32, size_t n, size_t rows, int n_cus) {
+    FoldPlan pl;
+    const size_t target = (size_t)n_cus * 16;
+    size_t chunks = 1;
+    if (rows && rows < target && n >= 8192) chunks = std::min<size_t>({(target + rows - 1) / rows, n / 4096, (size_t)1024});
+    pl.chunk = chunks > 1 ? ((n + chunks - 1) / chunks + 255) / 256 * 256 : std::max<size_t>(n, 1);
+    pl.chunks = std::max<size_t>(1, (n + pl.chunk - 1) / pl.chunk);
+    if (pl.chunks > 1) pl.partial_bytes = std::max<size_t>(pl.chunks * rows * w32 * 4, (size_t)1 << 20);
+    return pl;
+}
+
 struct GroupFoldPlan {
     uint32_t groups_per_pass = 0;  // groups of every pass but the last: pass k holds [k * gpp, min(G, (k + 1) * gpp))
     uint32_t passes = 0;
@@ -128,8 +151,8 @@ inline GroupFoldPlan plan_group_fold(int w32, size_t n, size_t rows, size_t n_gr
     pl.lds_bytes = (size_t)pl.copies * gpp * slot;
     pl.grid_x = (uint32_t)rows;
     if (n == 0 || rows == 0) return pl;
-    // chunks: enough workgroups to fill the chip when the rows are few (the
-    // rule of the ungrouped fold), bounded by the chunk length that amortises
+    // chunks: enough workgroups to fill the chip when the rows are few
+    // (plan_fold's rule), bounded by the chunk length that amortises
     // a chunk's partials, the partials budget and the int element count of
     // k_fold_shares
     const size_t target = (size_t)std::max(1, n_cus) * 16;

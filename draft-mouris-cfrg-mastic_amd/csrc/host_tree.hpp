@@ -1,7 +1,7 @@
 // Host-only decoding of an encoded agg param (poc/mastic.py:413-435,
 // Mastic.encode_agg_param) and the evaluated prefix tree of
 // eval_with_siblings (poc/vidpf.py:213-261).  Plain C++17, no HIP: the
-// library builds its device tree from it (mastic_hip.hip build_tree), and the
+// library builds its device tree from it (prep.hpp build_tree), and the
 // host sanitizer / fuzz test (tests/host/fuzz_host.cpp, built with
 // -fsanitize=address,undefined) drives it with malformed and random inputs.
 //

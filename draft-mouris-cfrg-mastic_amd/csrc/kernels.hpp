@@ -787,14 +787,6 @@ MH_D void parent_payload(const AesPerm& TL, const RkLds& rkc, const uint32_t cv[
 // ds_read_b128 per round) are shared by all 16 waves: 86 KiB per workgroup,
 // one workgroup = 4 waves per SIMD per CU.
 #define EVAL_WAVES 16
-// Counter groups (aes.hpp): rounds 1-2 shared by the blocks of one seed in
-// the extend pair, the convert seeds and the payload fast path.
-#ifndef MASTIC_EMIT_WAIT
-#define MASTIC_EMIT_WAIT 1
-#endif
-#ifndef MASTIC_CTR_GROUPS
-#define MASTIC_CTR_GROUPS 1
-#endif
 #define EVAL_PROOF_WAVES 8  // default split (schedule.hpp SchedKnobs::proof_waves); measured best of 2..12
 // VGPR cap of the level kernel: 4 waves x 96 per SIMD leave 128 of the 512
 // for one binder-sponge wave, so the two kernels can share a CU instead of
@@ -802,16 +794,12 @@ MH_D void parent_payload(const AesPerm& TL, const RkLds& rkc, const uint32_t cv[
 // 128) needs all of that; the 2-lane one (k_absorb_pair: 93, allocated 96)
 // leaves 32 more, which k_eval_aes_wide below takes.
 // (expressed as a minimum occupancy: 5 waves/SIMD <=> at most 96 VGPRs)
-#ifndef EVAL_MIN_WAVES
 #define EVAL_MIN_WAVES 5
-#endif
 // The frontier-cache instantiation (FC: a cache hit's one level, a cache-on
 // call's last level) runs with no binder-sponge waves beside it on a hit, so
 // it may take all 128 VGPRs of its 4 waves per SIMD (the LDS-resident tables
 // allow one workgroup per CU): no spills of the recompute / fused-proof state.
-#ifndef EVAL_FC_MIN_WAVES
 #define EVAL_FC_MIN_WAVES 4
-#endif
 #define EVAL_VGPR_ATTR __attribute__((amdgpu_waves_per_eu(FC ? EVAL_FC_MIN_WAVES : EVAL_MIN_WAVES)))
 // The plain variants beside 2-lane sponges (WIDE, k_eval_aes_wide): 104 VGPRs,
 // 4 x 104 + 96 = 512.  No occupancy gives 104, so the cap is amdgpu_num_vgpr,
@@ -1096,9 +1084,10 @@ MH_D void eval_aes_body(const McParams& p, const Planes& pl, const AesArgs& a) {
         // extend: block 0 -> left child, block 1 -> right child (one paired
         // AES call), correct, then both children's convert seed blocks.
         uint32_t cs0[4], cs1[4], ns0[4], ns1[4];
-#if MASTIC_CTR_GROUPS
         {
-            // both extend blocks share the parent seed (aes.hpp counter groups)
+            // both extend blocks share the parent seed (aes.hpp counter groups:
+            // rounds 1-2 shared by the blocks of one seed in the extend pair,
+            // the convert seeds and the payload fast path)
             AesCtrGroup gp;
             const uint32_t* const sd[1] = {ps};
             const uint32_t ch[1] = {0u};
@@ -1110,9 +1099,6 @@ MH_D void eval_aes_body(const McParams& p, const Planes& pl, const AesArgs& a) {
             uint32_t* const ov[2] = {cs0, cs1};
             ctr_blocks_n<2>(TL, rke, gg, sd2, cv, ov);
         }
-#else
-        fixed_key_block2(TL, rke, ps, 0u, ps, 1u, cs0, cs1);
-#endif
         uint32_t tc0 = cs0[0] & 1u, tc1 = cs1[0] & 1u;
         cs0[0] &= ~1u;
         cs1[0] &= ~1u;
@@ -1125,7 +1111,6 @@ MH_D void eval_aes_body(const McParams& p, const Planes& pl, const AesArgs& a) {
             tc0 ^= ccw & 1u;
             tc1 ^= (ccw >> 1) & 1u;
         }
-#if MASTIC_CTR_GROUPS
         // each child's convert stream (next seed: counter 0, payload blocks:
         // counters 1, 2, ...) is one counter group per 256 counters
         AesCtrGroup g0, g1;
@@ -1144,9 +1129,6 @@ MH_D void eval_aes_body(const McParams& p, const Planes& pl, const AesArgs& a) {
             uint32_t* const ov[2] = {ns0, ns1};
             ctr_blocks_n<2>(TL, rkc, gg, csd, cv, ov);
         }
-#else
-        if (kp == 0) fixed_key_block2(TL, rkc, cs0, 0u, cs1, 0u, ns0, ns1);
-#endif
         if constexpr (FC) {
             if (a.cache_out) {
                 // the last level's children as frontier-cache nodes: convert seed (payloads
@@ -1180,13 +1162,7 @@ MH_D void eval_aes_body(const McParams& p, const Planes& pl, const AesArgs& a) {
         // Element e of both children: payload correction, frontier payloads,
         // the parent's payload difference (or the root sum), out shares.
         uint32_t* const payg = a.payload + (size_t)blockIdx.x * a.pay_gstride;  // tiled group
-#ifdef MASTIC_EXPERIMENT_KNOBS
-        // timing experiments (results wrong): 8 = no frontier-payload stores,
-        // 16 = no parent-payload loads, 32 = no payload-difference stores
-        const bool x_fr = !(a.dbg_skip & 8), x_diff = !(a.dbg_skip & 32);
-#else
         constexpr bool x_fr = true, x_diff = true;
-#endif
         // payloads-format cache nodes of the two children (FC, AesArgs::out_nw > 5): their payload planes
         uint32_t* cpay0 = nullptr;
         uint32_t* cpay1 = nullptr;
@@ -1254,19 +1230,12 @@ MH_D void eval_aes_body(const McParams& p, const Planes& pl, const AesArgs& a) {
         }
         // level 0: the root's "parent payload" planes are zeroed by the host
         // (no branch, no zero-initialised registers in the block loop)
-#ifdef MASTIC_EXPERIMENT_KNOBS
-        const bool x_wp = !(a.dbg_skip & 16);
-        auto load_wp = [&](int e) { return x_wp ? pl_load<F>(wpb, wp_e0 + e, wp_S, r) : F::from_u64((uint64_t)e); };
-#else
         auto load_wp = [&](int e) { return pl_load<F>(wpb, wp_e0 + e, wp_S, r); };
-#endif
         int e_fast = e_lo;  // elements completed by the fast path
-#if MASTIC_EMIT_WAIT
         // the same before the block loop: the next parent's prefetched seed
         // and this parent's child-seed stores are long done; without it the
         // waitcnt pass keeps a vmcnt wait in the loop header (every block)
         __builtin_amdgcn_s_waitcnt(0x0F70);
-#endif
         if constexpr (FC) {
             if (fuse_ovl && lane == 0) {
                 // the child seeds / control bits above are stored: their proofs may start
@@ -1299,7 +1268,6 @@ MH_D void eval_aes_body(const McParams& p, const Planes& pl, const AesArgs& a) {
                     wpb = load_wp(e1);
                 }
                 uint32_t o0[4], o1[4];
-#if MASTIC_CTR_GROUPS
                 {
                     const uint32_t c = (uint32_t)(b + 1);
                     if ((c & ~0xffu) != g_hi) init_groups(c & ~0xffu);
@@ -1307,9 +1275,6 @@ MH_D void eval_aes_body(const McParams& p, const Planes& pl, const AesArgs& a) {
                     uint32_t* const ov[2] = {o0, o1};
                     ctr_blocks_n<2>(TL, rkc, gg, csd, cv, ov);
                 }
-#else
-                fixed_key_block2(TL, rkc, cs0, (uint32_t)(b + 1), cs1, (uint32_t)(b + 1), o0, o1);
-#endif
                 bool sus;
                 if constexpr (EPB == 2)
                     sus = (o0[1] == ~0u) | (o1[1] == ~0u) | (two & ((o0[3] == ~0u) | (o1[3] == ~0u)));
@@ -1328,9 +1293,7 @@ MH_D void eval_aes_body(const McParams& p, const Planes& pl, const AesArgs& a) {
                 // of the conditionally issued loads, waits for vmcnt(2..3)
                 // between the stores below, i.e. for the stores themselves to
                 // be acknowledged, several times per block.
-#if MASTIC_EMIT_WAIT
                 __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), expcnt / lgkmcnt untouched
-#endif
                 emit(e, F::from_words(o0), F::from_words(o1), cwa, wpa);
                 if constexpr (EPB == 2) {
                     if (two) emit(e + 1, F::from_words(o0 + 2), F::from_words(o1 + 2), cwb, wpb);
@@ -1529,12 +1492,7 @@ __global__ __launch_bounds__(256) void k_absorb(Planes pl, AbsorbArgs a) {
         if (!full) break;
         asm volatile("" ::: "memory");
         if (more) load_block(b + 1, cur);
-#ifdef MASTIC_EXPERIMENT_KNOBS
-        if (a.dbg == 3)
-            keccak_p12<2>(s);  // A/B only: rolled rounds (small code; same results)
-        else
-#endif
-            keccak_p12(s);
+        keccak_p12(s);
         if (!more) break;
     }
 #pragma unroll
@@ -1553,14 +1511,9 @@ __global__ __launch_bounds__(256) void k_absorb(Planes pl, AbsorbArgs a) {
 // i + 1 (h = 1), fetched with one DPP swap per word when the fill offset is not
 // a multiple of 4 (shifted byte image).  22 VGPRs of block buffer instead of
 // 42, so the kernel fits 5 waves per SIMD without spills.
-#ifndef ABSORB_MIN_WAVES
 #define ABSORB_MIN_WAVES 5
-#endif
-// partner exchanges through the LDS crossbar (keccak.hpp pair_swap<true>) instead
-// of DPP moves: measured, not adopted; 1 builds the A/B variant
-#ifndef MASTIC_PAIR_SWZ
-#define MASTIC_PAIR_SWZ 0
-#endif
+// (partner exchanges through the LDS crossbar, keccak.hpp pair_swap<true>, instead
+// of DPP moves: measured, not adopted; hence the `false` below)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ABSORB_MIN_WAVES)))
 void k_absorb_pair(Planes pl, AbsorbArgs a) {
     absorb_setprio(a.prio);
@@ -1643,13 +1596,13 @@ void k_absorb_pair(Planes pl, AbsorbArgs a) {
             // as a bitwise select: a C++ select of two array elements became a per-lane
             // index into a scratch copy of cur[]): one swap per word
             uint32_t nxt = 0u;
-            if (sh) nxt = pair_swap<MASTIC_PAIR_SWZ != 0>((uint32_t)__builtin_amdgcn_bitop3_b32(hmask, cur[i], cur[i + 1], 0xCA));
+            if (sh) nxt = pair_swap<false>((uint32_t)__builtin_amdgcn_bitop3_b32(hmask, cur[i], cur[i + 1], 0xCA));
             s.a[i] ^= __builtin_amdgcn_alignbit(nxt, cur[i], amt);
         }
         if (!full) break;
         asm volatile("" ::: "memory");
         if (more && a.dbg != 1 && a.dbg != 4) load_block(b + 1, cur);
-        if (a.dbg == 0 || a.dbg == 1) keccak_p12_pair<12, MASTIC_PAIR_SWZ != 0>(s, h != 0);
+        if (a.dbg == 0 || a.dbg == 1) keccak_p12_pair<12, false>(s, h != 0);
         else if (a.dbg == 4) __builtin_amdgcn_s_sleep(72);  // resident, ~4.6k cycles per block, no VALU
         if (!more) break;
     }

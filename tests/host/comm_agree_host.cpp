@@ -1,5 +1,5 @@
 // Host harness for the collective calls' agreement round
-// (draft-mouris-cfrg-mastic_amd/csrc/comm_agree.hpp, used by mastic_hip.hip
+// (draft-mouris-cfrg-mastic_amd/csrc/comm_agree.hpp, used by comm.hpp
 // comm_agree): N simulated ranks each contribute a status record, the
 // "all-gather" is the array of all records in rank order, and every rank
 // derives its return code from that same array.  Prints one line per case:

@@ -1,5 +1,5 @@
 // Test infrastructure only: a stand-in for the eight RCCL entry points
-// libmastic_hip binds (mastic_hip.hip, RcclApi), loaded through the
+// libmastic_hip binds (comm.hpp, RcclApi), loaded through the
 // MASTIC_RCCL_LIB test hook, so that several processes sharing ONE GPU can
 // form a communicator.  RCCL itself refuses two ranks on one device
 // ("Duplicate GPU detected"), and the builder has no multi-GPU box, so this is

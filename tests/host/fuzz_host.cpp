@@ -1,6 +1,6 @@
 // Host sanitizer + fuzz driver for the untrusted-input decoders of the
 // library: the agg-param decoder / tree builder
-// (csrc/host_tree.hpp, used by mastic_hip.hip build_tree) and the parameter
+// (csrc/host_tree.hpp, used by prep.hpp build_tree) and the parameter
 // derivation (csrc/params.hpp mc_derive, used by mastic_ctx_create).
 // Built by tests/test_host_sanitize.py with
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all

@@ -10,8 +10,11 @@
 //    without a mask;
 //  * plan_group_fold over a grid of shapes: the invariants the library and
 //    k_fold_grouped rely on, and a replay of the kernel's own indexing
-//    (every group in exactly one pass, every report in exactly one chunk).
-// Prints "plans checked: N" and "group_fold_host: OK".
+//    (every group in exactly one pass, every report in exactly one chunk);
+//  * plan_fold (the ungrouped fold) against a table of the values its
+//    expression returned before it moved out of the executor, and its
+//    invariants.
+// Prints "plans checked: N", "fold plans checked: N" and "group_fold_host: OK".
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -218,11 +221,160 @@ static size_t check_plans() {
     return checked;
 }
 
+// plan_fold (the ungrouped fold's chunking) pinned to the values the expression
+// returned while it stood inline in aggregate_impl (recorded from that code
+// before the move, not from plan_fold): n_cus, n, rows -> chunks, chunk, and
+// the partials buffer for Field64 / Field128.  The last two rows (a chip that
+// does not exist) are where the partials pass their 1 MiB floor.
+static size_t check_fold_plans() {
+    static const struct {
+        int n_cus;
+        size_t n, rows, chunks, chunk, part2, part4;
+    } want[] = {
+        {256, 0, 1, 1, 1, 0, 0},
+        {256, 0, 10, 1, 1, 0, 0},
+        {256, 0, 20, 1, 1, 0, 0},
+        {256, 0, 700, 1, 1, 0, 0},
+        {256, 0, 4095, 1, 1, 0, 0},
+        {256, 0, 4096, 1, 1, 0, 0},
+        {256, 0, 20000, 1, 1, 0, 0},
+        {256, 1, 1, 1, 1, 0, 0},
+        {256, 1, 10, 1, 1, 0, 0},
+        {256, 1, 20, 1, 1, 0, 0},
+        {256, 1, 700, 1, 1, 0, 0},
+        {256, 1, 4095, 1, 1, 0, 0},
+        {256, 1, 4096, 1, 1, 0, 0},
+        {256, 1, 20000, 1, 1, 0, 0},
+        {256, 8191, 1, 1, 8191, 0, 0},
+        {256, 8191, 10, 1, 8191, 0, 0},
+        {256, 8191, 20, 1, 8191, 0, 0},
+        {256, 8191, 700, 1, 8191, 0, 0},
+        {256, 8191, 4095, 1, 8191, 0, 0},
+        {256, 8191, 4096, 1, 8191, 0, 0},
+        {256, 8191, 20000, 1, 8191, 0, 0},
+        {256, 8192, 1, 2, 4096, 1048576, 1048576},
+        {256, 8192, 10, 2, 4096, 1048576, 1048576},
+        {256, 8192, 20, 2, 4096, 1048576, 1048576},
+        {256, 8192, 700, 2, 4096, 1048576, 1048576},
+        {256, 8192, 4095, 2, 4096, 1048576, 1048576},
+        {256, 8192, 4096, 1, 8192, 0, 0},
+        {256, 8192, 20000, 1, 8192, 0, 0},
+        {256, 8453, 1, 2, 4352, 1048576, 1048576},
+        {256, 8453, 10, 2, 4352, 1048576, 1048576},
+        {256, 8453, 20, 2, 4352, 1048576, 1048576},
+        {256, 8453, 700, 2, 4352, 1048576, 1048576},
+        {256, 8453, 4095, 2, 4352, 1048576, 1048576},
+        {256, 8453, 4096, 1, 8453, 0, 0},
+        {256, 8453, 20000, 1, 8453, 0, 0},
+        {256, 16384, 1, 4, 4096, 1048576, 1048576},
+        {256, 16384, 10, 4, 4096, 1048576, 1048576},
+        {256, 16384, 20, 4, 4096, 1048576, 1048576},
+        {256, 16384, 700, 4, 4096, 1048576, 1048576},
+        {256, 16384, 4095, 2, 8192, 1048576, 1048576},
+        {256, 16384, 4096, 1, 16384, 0, 0},
+        {256, 16384, 20000, 1, 16384, 0, 0},
+        {256, 1048576, 1, 256, 4096, 1048576, 1048576},
+        {256, 1048576, 10, 256, 4096, 1048576, 1048576},
+        {256, 1048576, 20, 205, 5120, 1048576, 1048576},
+        {256, 1048576, 700, 6, 174848, 1048576, 1048576},
+        {256, 1048576, 4095, 2, 524288, 1048576, 1048576},
+        {256, 1048576, 4096, 1, 1048576, 0, 0},
+        {256, 1048576, 20000, 1, 1048576, 0, 0},
+        {256, 2097152, 1, 512, 4096, 1048576, 1048576},
+        {256, 2097152, 10, 410, 5120, 1048576, 1048576},
+        {256, 2097152, 20, 205, 10240, 1048576, 1048576},
+        {256, 2097152, 700, 6, 349696, 1048576, 1048576},
+        {256, 2097152, 4095, 2, 1048576, 1048576, 1048576},
+        {256, 2097152, 4096, 1, 2097152, 0, 0},
+        {256, 2097152, 20000, 1, 2097152, 0, 0},
+        {64, 0, 1, 1, 1, 0, 0},
+        {64, 0, 10, 1, 1, 0, 0},
+        {64, 0, 20, 1, 1, 0, 0},
+        {64, 0, 700, 1, 1, 0, 0},
+        {64, 0, 4095, 1, 1, 0, 0},
+        {64, 0, 4096, 1, 1, 0, 0},
+        {64, 0, 20000, 1, 1, 0, 0},
+        {64, 1, 1, 1, 1, 0, 0},
+        {64, 1, 10, 1, 1, 0, 0},
+        {64, 1, 20, 1, 1, 0, 0},
+        {64, 1, 700, 1, 1, 0, 0},
+        {64, 1, 4095, 1, 1, 0, 0},
+        {64, 1, 4096, 1, 1, 0, 0},
+        {64, 1, 20000, 1, 1, 0, 0},
+        {64, 8191, 1, 1, 8191, 0, 0},
+        {64, 8191, 10, 1, 8191, 0, 0},
+        {64, 8191, 20, 1, 8191, 0, 0},
+        {64, 8191, 700, 1, 8191, 0, 0},
+        {64, 8191, 4095, 1, 8191, 0, 0},
+        {64, 8191, 4096, 1, 8191, 0, 0},
+        {64, 8191, 20000, 1, 8191, 0, 0},
+        {64, 8192, 1, 2, 4096, 1048576, 1048576},
+        {64, 8192, 10, 2, 4096, 1048576, 1048576},
+        {64, 8192, 20, 2, 4096, 1048576, 1048576},
+        {64, 8192, 700, 2, 4096, 1048576, 1048576},
+        {64, 8192, 4095, 1, 8192, 0, 0},
+        {64, 8192, 4096, 1, 8192, 0, 0},
+        {64, 8192, 20000, 1, 8192, 0, 0},
+        {64, 8453, 1, 2, 4352, 1048576, 1048576},
+        {64, 8453, 10, 2, 4352, 1048576, 1048576},
+        {64, 8453, 20, 2, 4352, 1048576, 1048576},
+        {64, 8453, 700, 2, 4352, 1048576, 1048576},
+        {64, 8453, 4095, 1, 8453, 0, 0},
+        {64, 8453, 4096, 1, 8453, 0, 0},
+        {64, 8453, 20000, 1, 8453, 0, 0},
+        {64, 16384, 1, 4, 4096, 1048576, 1048576},
+        {64, 16384, 10, 4, 4096, 1048576, 1048576},
+        {64, 16384, 20, 4, 4096, 1048576, 1048576},
+        {64, 16384, 700, 2, 8192, 1048576, 1048576},
+        {64, 16384, 4095, 1, 16384, 0, 0},
+        {64, 16384, 4096, 1, 16384, 0, 0},
+        {64, 16384, 20000, 1, 16384, 0, 0},
+        {64, 1048576, 1, 256, 4096, 1048576, 1048576},
+        {64, 1048576, 10, 103, 10240, 1048576, 1048576},
+        {64, 1048576, 20, 52, 20224, 1048576, 1048576},
+        {64, 1048576, 700, 2, 524288, 1048576, 1048576},
+        {64, 1048576, 4095, 1, 1048576, 0, 0},
+        {64, 1048576, 4096, 1, 1048576, 0, 0},
+        {64, 1048576, 20000, 1, 1048576, 0, 0},
+        {64, 2097152, 1, 512, 4096, 1048576, 1048576},
+        {64, 2097152, 10, 103, 20480, 1048576, 1048576},
+        {64, 2097152, 20, 52, 40448, 1048576, 1048576},
+        {64, 2097152, 700, 2, 1048576, 1048576, 1048576},
+        {64, 2097152, 4095, 1, 2097152, 0, 0},
+        {64, 2097152, 4096, 1, 2097152, 0, 0},
+        {64, 2097152, 20000, 1, 2097152, 0, 0},
+        {8192, 2097152, 700, 187, 11264, 1048576, 2094400},
+        {8192, 2097152, 20000, 7, 299776, 1120000, 2240000},
+    };
+    size_t checked = 0, split = 0;
+    for (const auto& w : want) {
+        const FoldPlan a = plan_fold(2, w.n, w.rows, w.n_cus), b = plan_fold(4, w.n, w.rows, w.n_cus);
+        CHECK(a.chunks == w.chunks && a.chunk == w.chunk && a.partial_bytes == w.part2);
+        CHECK(b.chunks == w.chunks && b.chunk == w.chunk && b.partial_bytes == w.part4);
+        // what k_fold's grid (rows, chunks) and its chunk argument rely on
+        if (a.chunks > 1) CHECK(a.chunk % 256 == 0);
+        CHECK(a.chunk >= 1 && a.chunks >= 1 && a.chunks <= 1024);
+        CHECK(a.chunks * a.chunk >= w.n);
+        CHECK((a.chunks - 1) * a.chunk < std::max<size_t>(w.n, 1));  // no empty chunk (an empty batch: its one chunk)
+        CHECK((a.partial_bytes == 0) == (a.chunks == 1));
+        if (a.chunks > 1) CHECK(a.partial_bytes >= a.chunks * w.rows * 2 * 4 && a.partial_bytes >= ((size_t)1 << 20));
+        if (b.chunks > 1) CHECK(b.partial_bytes >= b.chunks * w.rows * 4 * 4);
+        checked++;
+        split += a.chunks > 1;
+    }
+    CHECK(checked >= 2 * 8 * 7 && split > 0);
+    // the shapes tests/test_gpu_aggregate_grouped.py::test_one_group_is_the_ungrouped_fold runs split
+    CHECK(plan_fold(2, 8453, 10, 256).chunks == 2 && plan_fold(2, 8453, 10, 256).chunk == 4352);
+    CHECK(plan_fold(4, 8453, 20, 256).chunks == 2);
+    return checked;
+}
+
 int main() {
     check_limbs<F64>("F64");
     check_limbs<F128>("F128");
     check_ids();
     printf("plans checked: %zu\n", check_plans());
+    printf("fold plans checked: %zu\n", check_fold_plans());
     printf("group_fold_host: OK\n");
     return 0;
 }

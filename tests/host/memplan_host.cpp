@@ -1,5 +1,5 @@
 // Host harness for the memory plan of a prep_init
-// (draft-mouris-cfrg-mastic_amd/csrc/memplan.hpp, executed by mastic_hip.hip
+// (draft-mouris-cfrg-mastic_amd/csrc/memplan.hpp, executed by prep.hpp
 // mastic_prep_init).  Two parts:
 //   (a) frontier_hit, spare_capacity and the chunking (arena_fits, call_budget,
 //       plan_arena, plan_chunks) over a grid of inputs, against values recorded

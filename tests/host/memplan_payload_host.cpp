@@ -1,6 +1,6 @@
 // Host harness for the frontier cache's node formats in the memory plan
 // (draft-mouris-cfrg-mastic_amd/csrc/memplan.hpp: FrontierMeta::node_words,
-// slot_holds, spare_slot_words, choose_node_words; executed by mastic_hip.hip
+// slot_holds, spare_slot_words, choose_node_words; executed by prep.hpp
 // cache_slots).  Checks
 //   (a) frontier_hit accepts a cached level of either node width and
 //       frontier_commit records the width;

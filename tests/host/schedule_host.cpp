@@ -1,5 +1,5 @@
 // Host harness for the launch plan of a prep_init chunk
-// (draft-mouris-cfrg-mastic_amd/csrc/schedule.hpp, executed by mastic_hip.hip
+// (draft-mouris-cfrg-mastic_amd/csrc/schedule.hpp, executed by prep.hpp
 // struct Chunk).  Two parts:
 //   (a) the level-geometry helpers over a grid of inputs, against values
 //       recorded from the helpers' text before it moved into schedule.hpp

@@ -340,7 +340,7 @@ extern "C" int xof_ops_absorb(int pair, int layout, int n, int stride, size_t nc
         ab.which0 = 0;
         if (k[5]) e = hipMemcpyAsync(dsp.p, dinit.p, plane_bytes, hipMemcpyDeviceToDevice, 0);
         if (e != hipSuccess) break;
-        // the grid shapes of mastic_hip.hip's run_chunk
+        // the grid shapes of prep.hpp's Chunk
         if (pair)
             hipLaunchKernelGGL(k_absorb_pair, dim3((unsigned)((groups * 64 * 2 + 255) / 256), 2), dim3(256), 0, 0, pl,
                                ab);

@@ -65,11 +65,11 @@ def test_package_exports_no_group_and_metrics():
 def test_group_fold_header_is_host_only():
     """csrc/group_fold.hpp holds the plan and the arithmetic and includes no
     HIP header (it compiles with a plain host compiler once a field type is
-    given); mastic_hip.hip takes every decision from it."""
+    given); the fold executor, csrc/fold.hpp, takes every decision from it."""
     text = open(os.path.join(ROOT, "draft-mouris-cfrg-mastic_amd", "csrc", "group_fold.hpp")).read()
     code = re.sub(r"//.*", "", text)
     assert "#include <hip" not in code and '#include "' not in code
     for name in ("check_groups", "plan_group_fold", "limbs_to_elem"):
         assert re.search(r"\b%s\b" % name, code), name
-    hip = open(os.path.join(ROOT, "draft-mouris-cfrg-mastic_amd", "csrc", "mastic_hip.hip")).read()
-    assert "plan_group_fold(" in hip and "check_groups(" in hip
+    hip = open(os.path.join(ROOT, "draft-mouris-cfrg-mastic_amd", "csrc", "fold.hpp")).read()
+    assert "plan_group_fold(" in hip and "check_groups(" in hip and "plan_fold(" in hip

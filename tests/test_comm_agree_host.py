@@ -1,5 +1,5 @@
 """The N-rank decision of the collective calls' agreement round
-(csrc/comm_agree.hpp, mastic_hip.hip comm_agree; include/mastic_hip.h
+(csrc/comm_agree.hpp, comm.hpp comm_agree; include/mastic_hip.h
 "failure model"), on the host under ASan/UBSan with 8 simulated ranks: no
 rank ever proceeds to the data all-gather unless every rank is ready; a rank
 whose local work failed returns its own code, every other rank the lowest

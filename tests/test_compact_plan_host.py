@@ -1,5 +1,5 @@
 """The plan of mastic_reports_compact (csrc/compact_plan.hpp, which
-mastic_hip.hip executes with k_gather_rows and device-to-device copies), on the
+reports.hpp executes with k_gather_rows and device-to-device copies), on the
 host under ASan/UBSan.  tests/host/compact_plan_host.cpp runs every plan on a
 byte array with launch semantics, over random masks, all kept, none kept, only
 the first dropped, only the last kept, alternating and a dropped run inside a

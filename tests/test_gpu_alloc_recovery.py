@@ -2,7 +2,7 @@
 
 A result buffer or frontier-cache slot that cannot be allocated makes
 prep_init wait for everything queued on the ctx's three streams, free the
-retired buffers and the work arena, and retry (mastic_hip.hip
+retired buffers and the work arena, and retry (ctx.hpp
 ``mastic_ctx::reclaim_ensure`` with ``RECLAIM_ALL``, from ``size_results`` and
 ``cache_slots``).  At full scale only C3's 2M-report sweep reaches it, so
 the result-preserving ``fail_allocs`` test hook (``mastic_set_test_hooks``)

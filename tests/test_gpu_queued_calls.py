@@ -5,7 +5,7 @@ another verify key (which rebuilds the prefix states), results fetched in
 either order or folded straight from HBM.  A single-chunk cache-on call runs
 its binder sponges in the cache's own planes and the level kernel writes the
 out shares straight into the aggregator's result planes
-(csrc/mastic_hip.hip Chunk::run, "direct"), so the two aggregators' queued
+(csrc/prep.hpp Chunk::run, "direct"), so the two aggregators' queued
 calls share the work planes but not these.  Every result must equal a
 cache-off context's."""
 import random

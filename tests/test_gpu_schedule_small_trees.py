@@ -1,5 +1,5 @@
 """The launch plan's small-tree corners on the GPU against the oracle, bit for
-bit (csrc/schedule.hpp plan_chunk, executed by mastic_hip.hip struct Chunk).
+bit (csrc/schedule.hpp plan_chunk, executed by prep.hpp struct Chunk).
 
 Trees of depth L = 0, 1, 2 and 3 -- no sponge before the final step at L = 0,
 the first reuse of a level-buffer ring slot at L = 3, every level but the last

@@ -1,6 +1,6 @@
 """The memory plan of a prep_init (csrc/memplan.hpp: the frontier cache's hit
 test and commit, the spare slot's growth rule, and the chunking that
-mastic_hip.hip mastic_prep_init executes), on the host under ASan/UBSan.
+prep.hpp mastic_prep_init executes), on the host under ASan/UBSan.
 tests/host/memplan_host.cpp checks that the functions return what the text of
 mastic_prep_init returned before it moved there, over a grid of batch sizes,
 per-report layouts, paddings, arena states, free-memory figures, explicit

@@ -1,5 +1,5 @@
 """The launch plan of a prep_init chunk (csrc/schedule.hpp: the level-geometry
-helpers and plan_chunk, which mastic_hip.hip struct Chunk executes), on the host
+helpers and plan_chunk, which prep.hpp struct Chunk executes), on the host
 under ASan/UBSan.  tests/host/schedule_host.cpp checks that the helpers return
 the values recorded before they moved out of mastic_hip.hip, and that every
 plan over a grid of tree depths and widths, both fields, hit / miss, cache

@@ -24,13 +24,15 @@ for f in $(git -C "$ROOT" ls-tree --name-only "$COMMIT" draft-mouris-cfrg-mastic
 done
 git -C "$ROOT" show "$COMMIT:include/mastic_hip.h" > "$D/include/mastic_hip.h"
 python3 - "$ROOT" "$D" <<'EOF'
-import re, sys
+import glob, re, sys
 root, d = sys.argv[1], sys.argv[2]
 sys.path.insert(0, root + "/draft-mouris-cfrg-mastic_amd")
 from mastic_amd import _lib
 src_path = d + "/csrc/mastic_hip.hip"
 src = open(src_path).read()
-defined = set(re.findall(r'extern "C"[^(]*?\b(mastic_[a-z_0-9]+)\s*\(', src))
+# (the entry points are defined in mastic_hip.hip or in the headers it includes)
+every = "".join(open(f).read() for f in glob.glob(d + "/csrc/*"))
+defined = set(re.findall(r'extern "C"[^(]*?\b(mastic_[a-z_0-9]+)\s*\(', every))
 app = ["", "// ---- A/B build only (tools/build_ab_old.sh): the current binding's entry points",
        "#undef mastic_abi_version",
        'extern "C" int mastic_abi_version(void) { return %d; }' % _lib.ABI_VERSION]
