@@ -1,5 +1,5 @@
 // The host side of the folds (C++17; no HIP): for mastic_aggregate_grouped the
-// check of the group ids, the launch plan of k_fold_grouped (kernels.hpp) and
+// check of the group ids, the launch plan of k_fold_grouped (fold_kernels.hpp) and
 // the exact recombination of its integer word sums into a field element; for
 // the ungrouped fold the chunking of k_fold (plan_fold).  fold.hpp executes
 // the plans and decides nothing itself; tests/host/group_fold_host.cpp checks

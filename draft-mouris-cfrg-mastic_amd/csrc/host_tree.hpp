@@ -21,7 +21,7 @@
 enum { TREE_OK = 0, TREE_EINVAL = -22, TREE_ENOMEM = -12 };
 
 // Node paths are at most 8 words (256 bits) in the level kernels
-// (kernels.hpp node_proof_one, AesArgs child paths): BITS <= 256 covers
+// (node_proof.hpp node_proof_one, level_kernel.hpp AesArgs child paths): BITS <= 256 covers
 // every BASELINE config (C3 is BITS = 256).
 constexpr int TREE_MAX_BITS = 256;
 // Nodes of one tree (the host arrays hold 40 B per node, the device ones 44 B)

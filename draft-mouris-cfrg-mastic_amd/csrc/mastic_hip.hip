@@ -1,7 +1,8 @@
 // Host side of the MI355X Mastic aggregator, the C ABI of include/mastic_hip.h:
 // the library's one translation unit (every kernel is instantiated once).  No
 // CPU compute path exists: every cryptographic operation runs in the kernels
-// of kernels.hpp / shard.hpp.  Each subsystem's executor is a header of
+// of the device headers (kernels.hpp is their index; DESIGN.md "Device
+// sources") and shard.hpp.  Each subsystem's executor is a header of
 // definitions included below, once (DESIGN.md "Host sources" maps them); here
 // are the ctx's creation and teardown and the small setters and getters.
 #include "mastic_hip.h"

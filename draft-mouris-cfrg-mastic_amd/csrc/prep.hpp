@@ -281,7 +281,7 @@ static int copy_planes(mastic_ctx* c, DevBuf& dst, size_t dst_stride, size_t dst
 }
 
 // ---------------------------------------------------------------- prep_init
-// The level kernel of each variant (kernels.hpp eval_aes_body; schedule.hpp
+// The level kernel of each variant (level_kernel.hpp eval_aes_body; schedule.hpp
 // LEVEL_VARIANTS lists the legal ones): the launch path and the LDS attribute
 // loop of mastic_ctx_create both go through here.
 typedef void (*LevelKernel)(McParams, Planes, AesArgs);
@@ -334,7 +334,7 @@ struct Chunk {
     // and the root sum in the cache's planes (same stride): a hit resumes and
     // updates them in place, a miss fills them; no copies in or out.
     bool direct;
-    // tiled level buffers (kernels.hpp AbsorbArgs): words per report group,
+    // tiled level buffers (absorb_kernels.hpp AbsorbArgs): words per report group,
     // and between consecutive words of a report
     int oh_gstride, pay_gstride;
     static constexpr int bin_rstride = 64;
@@ -496,8 +496,9 @@ struct Chunk {
             ab.f[1] = s.f_pl;
             // The priority and debug arguments of AbsorbArgs and AesArgs were
             // experiment knobs; their A/Bs are settled and the executor pins the
-            // values.  The fields stay in kernels.hpp because taking them out
-            // moves the kernels' register allocation (DESIGN.md "Retired knobs").
+            // values.  The fields stay in the argument structs (absorb_kernels.hpp,
+            // level_kernel.hpp) because taking them out moves the kernels'
+            // register allocation (DESIGN.md "Retired knobs").
             ab.prio = 3;
             ab.dbg = 0;
             if (as != c->stream) HIPCHK(c, hipStreamWaitEvent(as, ready, 0));
@@ -1077,7 +1078,7 @@ extern "C" int mastic_decide_results(mastic_ctx* c, const uint8_t* app_ctx, size
     return 0;
 }
 
-// Eval-proof Merkle tree (proof-aggregation mode, kernels.hpp k_proof_tree_*)
+// Eval-proof Merkle tree (proof-aggregation mode, decide_kernels.hpp k_proof_tree_*)
 // over the last prep_init result of agg_id.
 extern "C" int mastic_proof_tree(mastic_ctx* c, int agg_id, const uint8_t* app_ctx, size_t ctx_len,
                                  uint8_t* nodes_out, size_t n_nodes) {

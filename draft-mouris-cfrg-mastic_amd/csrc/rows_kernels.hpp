@@ -48,6 +48,7 @@ struct __attribute__((packed, aligned(4))) RowsWords4 {
     uint32_t w[4];
 };
 
+// (k_gather_rows, the row-gathering overload of compaction; decide_kernels.hpp has the planes-to-wire-rows one)
 __global__ __launch_bounds__(ROWS_THREADS) void k_gather_rows(const uint8_t* src, uint8_t* dst,
                                                               size_t row_bytes, const uint32_t* __restrict__ idx,
                                                               size_t first, size_t count, uint32_t slots_per_row) {

@@ -13,7 +13,7 @@
 // ------------------------------------------------------------ shared constants
 constexpr int NSLOT = 3;  // level buffers in flight between eval and absorb
 constexpr int LAST_LEVEL_SEGMENTS_AUTO = 4;
-// kernels.hpp EVAL_WAVES / EVAL_PROOF_WAVES and keccak.hpp KECCAK_RATE, which
+// level_kernel.hpp EVAL_WAVES / EVAL_PROOF_WAVES and keccak.hpp KECCAK_RATE, which
 // the kernels need as macros (mastic_hip.hip static_asserts that they agree)
 constexpr int SCHED_EVAL_WAVES = 16;
 constexpr int SCHED_EVAL_PROOF_WAVES = 8;
@@ -112,7 +112,7 @@ inline void choose_split(int n_parents, int np_prev, int proof_waves, int nblk, 
 }
 
 // Proof waves of a level kernel whose node proofs are fused and overlapped
-// (a frontier-cache hit, kernels.hpp fuse_ovl): the proofs' share of the work
+// (a frontier-cache hit, level_kernel.hpp fuse_ovl): the proofs' share of the work
 // per parent, two Keccak-p (VALU, ~3.2k CU-cycles) against the AES of the
 // extend pair, the convert seeds, both children's payload blocks and the
 // parent-payload recompute, 4 + 3 nblk blocks (LDS: 2 x 133 cycles per block
@@ -200,7 +200,7 @@ inline int last_level_segments(const SchedKnobs& c, const TreeShape& t, int grou
 }
 
 // ------------------------------------------------------------------- the plan
-// Level-kernel instantiations (kernels.hpp eval_aes_body's GEN / FC / SPLIT /
+// Level-kernel instantiations (level_kernel.hpp eval_aes_body's GEN / FC / SPLIT /
 // WIDE), as a bit set.  The legal ones: FC only with GEN and nothing else.
 // (LV_PAY is not the plan's: the launch adds it to an FC launch whose input or
 // output cache slot holds payloads-format nodes, memplan.hpp.)

@@ -3,7 +3,13 @@
 // synthesise reports at scale (bench) and behind the drop-in `shard`.
 // Writes the wire encodings straight into the report buffers.
 #pragma once
-#include "kernels.hpp"
+#include "aes.hpp"
+#include "conv_stream.hpp"
+#include "finish_kernels.hpp"
+#include "flp.hpp"
+#include "keccak.hpp"
+#include "params.hpp"
+#include "planes.hpp"
 
 struct ShardArgs {
     int n;

@@ -1,8 +1,9 @@
 // TEST INFRASTRUCTURE -- the XOF layer on the device (tests/test_gpu_xof_ops.py;
 // built by __graft_entry__.build_xof_ops into tests/host/_build/libxof_ops.so).
-// csrc/keccak.hpp's permutations and sponge functions, kernels.hpp's
-// node_proof_one, squeeze_elems, k_prefix_states, k_absorb and k_absorb_pair,
-// and csrc/aes.hpp's two fixed-key AES paths, each alone on chosen inputs: a
+// csrc/keccak.hpp's permutations and sponge functions, node_proof.hpp's
+// node_proof_one, finish_kernels.hpp's squeeze_elems, planes.hpp's
+// k_prefix_states, absorb_kernels.hpp's k_absorb and k_absorb_pair, and
+// csrc/aes.hpp's two fixed-key AES paths, each alone on chosen inputs: a
 // chosen sponge state, fill position, length, counter or key, which end to end
 // only an honest client's randomness and a handful of ctx lengths choose.
 //
@@ -18,7 +19,13 @@
 
 #include <vector>
 
-#include "kernels.hpp"
+#include "absorb_kernels.hpp"
+#include "aes.hpp"
+#include "finish_kernels.hpp"
+#include "flp.hpp"
+#include "keccak.hpp"
+#include "node_proof.hpp"
+#include "planes.hpp"
 
 namespace {
 

@@ -1,6 +1,7 @@
 """The XOF layer's device code alone, bit for bit against a plain reference.
 tests/host/xof_ops.hip (a test-only library built by build()) runs csrc/keccak.hpp,
-csrc/aes.hpp and the sponge and node-proof code of csrc/kernels.hpp on chosen
+csrc/aes.hpp and the sponge and node-proof code of csrc/absorb_kernels.hpp,
+finish_kernels.hpp, planes.hpp and node_proof.hpp on chosen
 inputs; end to end those functions only see what an honest client's randomness
 and a handful of ctx lengths produce.  The reference is tests/xof_ref.py
 (pinned by tests/test_xof_ref.py, which also holds the case lists of
