@@ -19,10 +19,13 @@ what is computed:
     RCCL all-gather + GPU mod-p fold), so each level's pruning decision is
     taken on the job-wide aggregate and all ranks walk the same frontier.
 """
-import time
+import contextlib
 
 import numpy as np
 
+# joint_rand_confirmed and _encode_reports lived here once and stay importable from here
+from .rounds import (PhaseClock, Round, admit, encode_reports as _encode_reports,  # noqa: F401
+                     joint_rand_confirmed, on_device, resident, unshard_raw as _unshard_raw)
 from .vdaf import Mastic
 
 
@@ -38,14 +41,6 @@ def get_threshold(thresholds, prefix):
     return thresholds['default']
 
 
-def _encode_reports(mastic: Mastic, reports):
-    nonces = b"".join(r[0] for r in reports)
-    pubs = b"".join(mastic.encode_public_share(r[1]) for r in reports)
-    in0 = b"".join(mastic.test_vec_encode_input_share(r[2][0]) for r in reports)
-    in1 = b"".join(mastic.test_vec_encode_input_share(r[2][1]) for r in reports)
-    return (nonces, pubs, in0, in1)
-
-
 def _child_packed(packed: bytes, level: int, bit: bool) -> bytes:
     """MSB-first packing (vidpf.py:33-39) of ``prefix + (bit,)`` from the
     packing of the length-``level`` ``prefix``."""
@@ -56,54 +51,9 @@ def _child_packed(packed: bytes, level: int, bit: bool) -> bytes:
     return packed
 
 
-def _unshard_raw(mastic: Mastic, raw_shares, num_measurements):
-    """``mastic.unshard`` (mastic.py:399-411) on encode_vec agg shares (the
-    two aggregators', or one already-merged total), summed as integers mod p
-    (same result, without a field object per share element; Field64 in
-    numpy: 2^64 = 2^32 - 1 mod p)."""
-    f = mastic.field
-    enc = f.ENCODED_SIZE
-    p = f.MODULUS
-    k = 1 + mastic.OUTPUT_LEN
-    if enc == 8:
-        acc = None
-        for r in raw_shares:
-            v = np.frombuffer(r, dtype="<u8")
-            if v.size and int(v.max()) >= p:
-                raise ValueError("encoded element out of range")
-            if acc is None:
-                acc = v.copy()
-                continue
-            t = acc + v  # wraps mod 2^64
-            t += (t < acc).astype(np.uint64) * np.uint64(0xFFFFFFFF)
-            acc = np.where(t >= np.uint64(p), t - np.uint64(p), t)
-        ints = [] if acc is None else acc.tolist()
-    else:
-        vecs = [[int.from_bytes(r[i:i + enc], "little") for i in range(0, len(r), enc)] for r in raw_shares]
-        for v in vecs:
-            if v and max(v) >= p:
-                raise ValueError("encoded element out of range")
-        ints = [sum(col) % p for col in zip(*vecs)]
-    if mastic.circuit in ("Count", "Sum"):  # Mastic.decode_result: the one output element
-        return ints[1::k]
-    return [ints[i + 1:i + k] for i in range(0, len(ints), k)]
-
-
 def _unpack_prefix(packed: bytes, length: int):
     """The tuple of bools of an MSB-first packed prefix (vidpf.py:33-39)."""
     return tuple(bool((packed[i // 8] >> (7 - i % 8)) & 1) for i in range(length))
-
-
-def joint_rand_confirmed(msgs: bytes, jr_seeds_0: bytes, jr_seeds_1: bytes, n: int):
-    """Per report: ``prep_next``'s joint-rand confirmation (mastic.py:369-375)
-    for both aggregators -- the prep message (the seed recomputed from both
-    parts, ``prep_shares_to_prep``) equals each aggregator's own seed."""
-    if n == 0:
-        return np.ones(0, dtype=bool)
-    m = np.frombuffer(msgs, np.uint8, count=32 * n).reshape(n, 32)
-    j0 = np.frombuffer(jr_seeds_0, np.uint8, count=32 * n).reshape(n, 32)
-    j1 = np.frombuffer(jr_seeds_1, np.uint8, count=32 * n).reshape(n, 32)
-    return (m == j0).all(axis=1) & (m == j1).all(axis=1)
 
 
 class SweepLevel:
@@ -116,27 +66,123 @@ class SweepLevel:
         self.n_valid = n_valid
 
 
+class Frontier:
+    """The sweep's candidate prefixes, level by level: both one-bit prefixes
+    at level 0, then the two children of every candidate whose aggregate
+    reached its threshold (:func:`get_threshold`).
+
+    The candidates are kept in the forms the sweep needs, decided here, once.
+    The device form (``device``) takes the encoded aggregation parameter from
+    the candidates' MSB-first packings (``packed``), each extended from its
+    parent's instead of re-packed bit by bit; the wire form encodes the bool
+    tuples (``prefixes``).  The tuples are left out altogether (``lazy``, and
+    then ``prefixes`` is None) when nothing asks for them: the device form, no
+    ``trace``, one default threshold, and no ``merge`` that is told the
+    level's candidates (``begin_level``) or folds field-object shares (one
+    without ``total``)."""
+
+    def __init__(self, bits: int, thresholds, device: bool, trace=None, merge=None):
+        self.bits = bits
+        self.thresholds = thresholds
+        self.lazy = (device and trace is None and len(thresholds) == 1
+                     and (merge is None or (hasattr(merge, "total") and not hasattr(merge, "begin_level"))))
+        self.packed = [b"\x00", b"\x80"] if device else None
+        self.prefixes = None if self.lazy else [(False,), (True,)]
+        self.heavy_hitters = []
+
+    @property
+    def n_cand(self):
+        return len(self.prefixes if self.packed is None else self.packed)
+
+    def agg_param(self, level: int):
+        """The level's aggregation parameter for ``is_valid``, ``agg_init`` and
+        ``unshard`` (lazy: without the prefixes)."""
+        return (level, () if self.lazy else tuple(self.prefixes), level == 0)
+
+    def encode(self, mastic, agg_param) -> bytes:
+        """``agg_param`` encoded, once per level (the batch calls take the bytes)."""
+        if self.packed is None:
+            return mastic.encode_agg_param(agg_param)
+        (level, _prefixes, weight_check) = agg_param
+        return (level.to_bytes(2, "big") + len(self.packed).to_bytes(4, "big") + b"".join(self.packed)
+                + bytes([int(weight_check)]))
+
+    def prune(self, level: int, agg_result):
+        """Keep the candidates whose aggregate reaches their threshold: their
+        children are the next level's candidates, and at the last level they
+        are the heavy hitters."""
+        if self.lazy:
+            th = self.thresholds['default']
+            keep = [i for (i, count) in enumerate(agg_result) if count >= th]
+        else:
+            keep = [i for (i, (prefix, count)) in enumerate(zip(self.prefixes, agg_result))
+                    if count >= get_threshold(self.thresholds, prefix)]
+        if level == self.bits - 1:
+            self.heavy_hitters = [_unpack_prefix(self.packed[i], self.bits) if self.lazy else self.prefixes[i]
+                                  for i in keep]
+            return
+        if not self.lazy:
+            self.prefixes = [self.prefixes[i] + (bit,) for i in keep for bit in (False, True)]
+        if self.packed is not None:
+            self.packed = [_child_packed(self.packed[i], level + 1, bit) for i in keep for bit in (False, True)]
+
+
+def _folds(mastic, merge, device: bool, lazy: bool):
+    """``(fold, fold_empty)``: how a level's aggregate is made after a round
+    and without one (no reports, or no candidates).  Each is a pair
+    ``(shares, unshard)``: ``shares(enc, mask, agg_param, n_cand)`` gives the
+    level's agg shares (``mask``: the round's accept mask, None without a
+    round, and then agg_init's zeros for every candidate), and
+    ``unshard(agg_param, shares, num_measurements)`` the aggregate."""
+    n_elems = 1 + mastic.OUTPUT_LEN  # per candidate
+
+    def merged(enc, mask, agg_param, n_cand):
+        # both shares folded, gathered and merged in HBM (one RCCL call); a rank
+        # without a round still calls, so that every rank issues the same collectives
+        if mask is None:
+            return [merge.total(n_cand * n_elems, have_results=False)]
+        return [merge.total(n_cand * n_elems, mask)]
+
+    def raw(enc, mask, agg_param, n_cand):
+        if mask is None:
+            return [bytes(n_cand * n_elems * mastic.field.ENCODED_SIZE)]
+        return [mastic.aggregate_device(agg_id, enc, mask, raw=True) for agg_id in range(2)]
+
+    def fields(enc, mask, agg_param, n_cand):
+        if mask is None:
+            return [mastic.agg_init(agg_param) for _ in range(2)]
+        return [mastic.aggregate_device(agg_id, enc, mask) for agg_id in range(2)]
+
+    def unshard_raw(agg_param, shares, num_measurements):
+        return _unshard_raw(mastic, shares, num_measurements)
+
+    def unshard_fields(agg_param, shares, num_measurements):
+        if merge is not None:
+            shares = [merge(a) for a in shares]
+        return mastic.unshard(agg_param, shares, num_measurements)
+
+    if device and merge is not None and hasattr(merge, "total"):
+        return ((merged, unshard_raw), (merged, unshard_raw))
+    # without a round the lazy agg param carries no prefix tuples for agg_init to count
+    return ((raw, unshard_raw) if device and merge is None else (fields, unshard_fields),
+            (raw, unshard_raw) if lazy else (fields, unshard_fields))
+
+
+@contextlib.contextmanager
+def _cache_nodes(mastic, mode):
+    """The frontier cache's node format set to ``mode`` and left as found
+    afterwards; None leaves the mastic's mode alone."""
+    found = None if mode is None else mastic.set_frontier_cache_nodes(mode)
+    try:
+        yield
+    finally:
+        if found is not None:
+            mastic.set_frontier_cache_nodes(found)
+
+
 def compute_heavy_hitters(mastic: Mastic, ctx: bytes, thresholds, reports, verify_key: bytes = None,
                           trace=None, merge=None, timing=None, frontier_cache=None, cached_levels=None,
                           phase_times=None, level_hook=None, cache_nodes=None, nonce_set=None, compact=None):
-    """:func:`_sweep` (which documents the other arguments) with the frontier
-    cache's node format ``cache_nodes`` (``'seeds'``, ``'payloads'`` or
-    ``'auto'``: ``Mastic.set_frontier_cache_nodes``) set before the sweep and
-    left as found afterwards; None leaves the mastic's mode alone."""
-    if cache_nodes is None:
-        return _sweep(mastic, ctx, thresholds, reports, verify_key, trace, merge, timing, frontier_cache,
-                      cached_levels, phase_times, level_hook, nonce_set, compact)
-    found = mastic.set_frontier_cache_nodes(cache_nodes)
-    try:
-        return _sweep(mastic, ctx, thresholds, reports, verify_key, trace, merge, timing, frontier_cache,
-                      cached_levels, phase_times, level_hook, nonce_set, compact)
-    finally:
-        mastic.set_frontier_cache_nodes(found)
-
-
-def _sweep(mastic: Mastic, ctx: bytes, thresholds, reports, verify_key: bytes = None,
-           trace=None, merge=None, timing=None, frontier_cache=None, cached_levels=None,
-           phase_times=None, level_hook=None, nonce_set=None, compact=None):
     """poc/examples.py:37-91 on the GPU.
 
     ``reports`` is either the reference's list of
@@ -183,166 +229,63 @@ def _sweep(mastic: Mastic, ctx: bytes, thresholds, reports, verify_key: bytes = 
     either way.  If ``reports`` is the caller's own :class:`Reports` batch,
     compaction mutates it: afterwards it holds the surviving reports only, in
     their order, and ``reports.n`` is their number.
+
+    ``cache_nodes`` (``'seeds'``, ``'payloads'`` or ``'auto'``:
+    ``Mastic.set_frontier_cache_nodes``) is the frontier cache's node format
+    for the sweep; the mastic's mode is left as found afterwards, and None
+    leaves it alone.
     """
     if compact is not None and not 0.0 <= compact <= 1.0:
         raise ValueError("compact must be None or a share in [0, 1]")
+    with _cache_nodes(mastic, cache_nodes):
+        if frontier_cache is not None:
+            mastic.set_frontier_cache(frontier_cache)
+        if verify_key is None:
+            import os
+            verify_key = os.urandom(16)  # gen_rand(16), examples.py:38
+        (dev, n) = resident(mastic, reports)
+        alive = admit(nonce_set, dev, n)
 
-    def clock(phase, t0):
-        if phase_times is not None:
-            t1 = time.perf_counter()
-            phase_times[phase] = phase_times.get(phase, 0.0) + t1 - t0
-            return t1
-        return t0
+        def drop_dead():
+            # the dead rows leave the batch; the survivors keep their order
+            nonlocal n, alive
+            dead = n - int(alive.sum())
+            if compact is not None and dead and dead >= compact * n:
+                n = dev.compact(alive)
+                alive = np.ones(n, dtype=bool)
 
-    if frontier_cache is not None:
-        mastic.set_frontier_cache(frontier_cache)
-    if verify_key is None:
-        import os
-        verify_key = os.urandom(16)  # gen_rand(16), examples.py:38
-    if isinstance(reports, (list, tuple)):
-        if len(reports) == 0:
-            dev = None
-        else:
-            dev = mastic.reports_upload(*_encode_reports(mastic, reports))
-    else:
-        dev = reports
-    n = 0 if dev is None else dev.n
-    alive = np.ones(n, dtype=bool)
-    if nonce_set is not None and n:
-        alive = np.asarray(nonce_set.admit(dev)) == 1
+        drop_dead()
 
-    def drop_dead():
-        # the dead rows leave the batch; the survivors keep their order
-        nonlocal n, alive
-        dead = n - int(alive.sum())
-        if compact is None or dead == 0 or dead < compact * n:
-            return
-        n = dev.compact(alive)
-        alive = np.ones(n, dtype=bool)
-
-    drop_dead()
-
-    prefixes = [(False,), (True,)]
-    fast = isinstance(mastic, Mastic)
-    packed = [b"\x00", b"\x80"]  # MSB-first packings of ``prefixes`` (fast path)
-    # lazy: the candidates only as packings (no bool tuples per level) when
-    # nothing asks for the tuples: no trace, one default threshold, and no
-    # merge that needs the level's candidates or field-object shares
-    lazy = (fast and trace is None and len(thresholds) == 1
-            and (merge is None or (hasattr(merge, "total") and not hasattr(merge, "begin_level"))))
-    if lazy:
-        prefixes = None
-        th = thresholds['default']
-    prev_agg_params = []
-    heavy_hitters = []
-    bits = mastic.vidpf.BITS
-    for level in range(bits):
-        n_cand = len(packed) if lazy else len(prefixes)
-        agg_param = (level, () if lazy else tuple(prefixes), level == 0)
-        assert mastic.is_valid(agg_param, prev_agg_params)
-        # encoded once per level (the batch calls take the bytes); the fast
-        # path extends the parents' packings instead of re-packing every bit
-        if fast:
-            enc = (level.to_bytes(2, "big") + n_cand.to_bytes(4, "big") + b"".join(packed)
-                   + bytes([int(level == 0)]))
-        else:
-            enc = mastic.encode_agg_param(agg_param)
-
-        device_merge = fast and merge is not None and hasattr(merge, "total")
-        if merge is not None and hasattr(merge, "begin_level"):
-            merge.begin_level(level, prefixes)  # merges that need the level's candidates
-        n_elems = n_cand * (1 + mastic.OUTPUT_LEN) if device_merge else 0
-        raw = agg_shares = None
-        tp = time.perf_counter() if phase_times is not None else 0.0
-        if n and n_cand:
-            # both aggregators' prep_init are queued before either result is
-            # fetched, so the host work of the second overlaps the GPU run of
-            # the first (stream-ordered; results and timings are per agg_id)
-            for agg_id in range(2):
-                mastic.prep_init_device(dev, verify_key, ctx, agg_id, enc)
-                if cached_levels is not None and agg_id == 0 and frontier_cache and mastic.last_prep_was_cached():
-                    cached_levels.append(level)
-            tp = clock("prep_init_enqueue", tp)
-            if fast:
-                # both aggregators' prep_shares_to_prep + prep_next on the GPU:
-                # the prep shares stay in HBM, only the accept mask comes back
-                (accept, _codes) = mastic.decide_results(ctx, n)
-                alive &= accept == 1
-                tp = clock("decide_wait", tp)
-                if timing is not None:
-                    for agg_id in range(2):
-                        mastic.select_timing(agg_id)
-                        timing.append(mastic.last_timing3())
-                tp = time.perf_counter() if phase_times is not None else 0.0
-            else:
-                shares = []
-                for agg_id in range(2):
-                    shares.append(mastic.prep_result(dev, agg_id, enc))
-                    if timing is not None:
-                        timing.append(mastic.last_timing3())
-                (msgs, valid) = mastic.decide_batch(ctx, enc, shares[0][0], shares[1][0])
-                alive &= (valid == 1) & (shares[0][3] == 0) & (shares[1][3] == 0)
-                if level == 0 and mastic.JOINT_RAND_LEN > 0:
-                    # prep_next (mastic.py:364-377, called at examples.py:67): each
-                    # aggregator's joint-rand seed must equal the prep message
-                    alive &= joint_rand_confirmed(msgs, shares[0][1], shares[1][1], n)
-            if level_hook is not None:
-                level_hook(level, enc, dev)
-            mask = alive.astype(np.uint8)
-            if device_merge:
-                # both shares folded, gathered and merged in HBM (one RCCL call)
-                raw = [merge.total(n_elems, mask)]
-            elif fast and merge is None:
-                raw = [mastic.aggregate_device(agg_id, enc, mask, raw=True) for agg_id in range(2)]
-            else:
-                agg_shares = [mastic.aggregate_device(agg_id, enc, mask) for agg_id in range(2)]
-        elif device_merge:
-            raw = [merge.total(n_elems, have_results=False)]  # same collectives on every rank
-        elif lazy:
-            # no reports: agg_init's zeros for every candidate (the lazy agg
-            # param carries no prefix tuples for agg_init to count)
-            raw = [bytes(n_cand * (1 + mastic.OUTPUT_LEN) * mastic.field.ENCODED_SIZE)]
-        else:
-            agg_shares = [mastic.agg_init(agg_param) for _ in range(2)]
-        tp = clock("aggregate_merge", tp)
-        if raw is not None:
-            agg_result = _unshard_raw(mastic, raw, int(alive.sum()))
-        else:
-            if merge is not None:
-                agg_shares = [merge(a) for a in agg_shares]
-            agg_result = mastic.unshard(agg_param, agg_shares, int(alive.sum()))
-        prev_agg_params.append(agg_param)
-        if trace is not None:
-            trace.append(SweepLevel(level, list(prefixes), agg_result, int(alive.sum())))
-        if level == 0:
-            drop_dead()
-
-        if lazy:
-            if level < bits - 1:
-                next_packed = []
-                for (pk, count) in zip(packed, agg_result):
-                    if count >= th:
-                        next_packed.append(_child_packed(pk, level + 1, False))
-                        next_packed.append(_child_packed(pk, level + 1, True))
-                packed = next_packed
-                clock("unshard_prune", tp)
-            else:
-                heavy_hitters = [_unpack_prefix(pk, bits) for (pk, count) in zip(packed, agg_result) if count >= th]
-        elif level < bits - 1:
-            next_prefixes = []
-            next_packed = []
-            for (i, (prefix, count)) in enumerate(zip(prefixes, agg_result)):
-                if count >= get_threshold(thresholds, prefix):
-                    next_prefixes.append(prefix + (False,))
-                    next_prefixes.append(prefix + (True,))
-                    if fast:
-                        next_packed.append(_child_packed(packed[i], level + 1, False))
-                        next_packed.append(_child_packed(packed[i], level + 1, True))
-            prefixes = next_prefixes
-            packed = next_packed
-            clock("unshard_prune", tp)
-        else:
-            for (prefix, count) in zip(prefixes, agg_result):
-                if count >= get_threshold(thresholds, prefix):
-                    heavy_hitters.append(prefix)
-    return heavy_hitters
+        device = on_device(mastic)
+        clock = PhaseClock(phase_times)
+        frontier = Frontier(mastic.vidpf.BITS, thresholds, device, trace, merge)
+        verify = Round(mastic, ctx, verify_key, timing, clock, cached_levels if frontier_cache else None)
+        (fold, fold_empty) = _folds(mastic, merge, device, frontier.lazy)
+        begin_level = getattr(merge, "begin_level", None)  # merges that need the level's candidates
+        prev_agg_params = []
+        for level in range(frontier.bits):
+            agg_param = frontier.agg_param(level)
+            assert mastic.is_valid(agg_param, prev_agg_params)
+            enc = frontier.encode(mastic, agg_param)
+            n_cand = frontier.n_cand
+            if begin_level is not None:
+                begin_level(level, frontier.prefixes)
+            clock.start()
+            ((shares, unshard), mask) = (fold_empty, None)
+            if n and n_cand:
+                verify(dev, enc, alive, level == 0, level)
+                if level_hook is not None:
+                    level_hook(level, enc, dev)
+                ((shares, unshard), mask) = (fold, alive.astype(np.uint8))
+            agg_shares = shares(enc, mask, agg_param, n_cand)
+            clock.mark("aggregate_merge")
+            agg_result = unshard(agg_param, agg_shares, int(alive.sum()))
+            prev_agg_params.append(agg_param)
+            if trace is not None:
+                trace.append(SweepLevel(level, list(frontier.prefixes), agg_result, int(alive.sum())))
+            if level == 0:
+                drop_dead()
+            frontier.prune(level, agg_result)
+            if level < frontier.bits - 1:
+                clock.mark("unshard_prune")
+        return frontier.heavy_hitters

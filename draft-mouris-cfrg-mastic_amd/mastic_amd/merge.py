@@ -20,6 +20,7 @@ rehearsals (RCCL refuses two ranks on one device).
 import ctypes
 
 from . import _lib
+from .vdaf import _mask
 
 
 def exchange_unique_id(m, rank: int, broadcast):
@@ -96,12 +97,10 @@ def aggregate_to_tensor(m, agg_id, n_elems, valid=None, out=None):
     uint8 tensor (``mastic_aggregate_device_on_stream``).  The library orders the fold
     after the work queued on torch's current stream (the tensor's allocation
     or fill) by an event."""
-    import numpy as np
     import torch
     if out is None:
         out = torch.empty(n_elems * m.field.ENCODED_SIZE, dtype=torch.uint8, device="cuda")
-    v = None if valid is None else np.ascontiguousarray(np.asarray(valid, dtype=np.uint8))
-    rc = _lib.lib().mastic_aggregate_device_on_stream(m._ctx, agg_id, _lib.buf(v),
+    rc = _lib.lib().mastic_aggregate_device_on_stream(m._ctx, agg_id, _lib.buf(_mask(valid)),
                                                       ctypes.c_void_p(out.data_ptr()), _current_stream_handle())
     if rc != 0:
         raise _lib.MasticError(rc, "mastic_aggregate_device_on_stream failed")

@@ -18,7 +18,7 @@ buckets there are.
 """
 import numpy as np
 
-from .heavy_hitters import _encode_reports, _unshard_raw, joint_rand_confirmed
+from .rounds import Round, admit, on_device, resident, unshard_raw
 from .vdaf import MAX_GROUPS, NO_GROUP, Mastic
 
 
@@ -54,11 +54,7 @@ def compute_attribute_metrics(mastic: Mastic, ctx: bytes, attributes, reports, v
     if verify_key is None:
         import os
         verify_key = os.urandom(16)  # gen_rand(16), examples.py:176
-    if isinstance(reports, (list, tuple)):
-        dev = mastic.reports_upload(*_encode_reports(mastic, reports)) if len(reports) else None
-    else:
-        dev = reports
-    n = 0 if dev is None else dev.n
+    (dev, n) = resident(mastic, reports)
     if groups is None:
         ids = np.zeros(n, np.uint32)
         n_groups = 1
@@ -72,25 +68,13 @@ def compute_attribute_metrics(mastic: Mastic, ctx: bytes, attributes, reports, v
     if not 1 <= n_groups <= MAX_GROUPS:
         raise ValueError("n_groups must be 1 .. %d" % MAX_GROUPS)
 
-    alive = np.ones(n, dtype=bool)
-    if nonce_set is not None and n:
-        alive = np.asarray(nonce_set.admit(dev)) == 1
-    fast = isinstance(mastic, Mastic)
+    alive = admit(nonce_set, dev, n)
+    fast = on_device(mastic)
     enc = mastic.encode_agg_param(agg_param)
     if n == 0:
         empty = mastic.unshard(agg_param, [mastic.agg_init(agg_param) for _ in range(2)], 0)
         return [(list(empty), 0) for _ in range(n_groups)]
-    for agg_id in range(2):
-        mastic.prep_init_device(dev, verify_key, ctx, agg_id, enc)
-    if fast:
-        (accept, _codes) = mastic.decide_results(ctx, n)
-        alive &= accept == 1
-    else:
-        shares = [mastic.prep_result(dev, agg_id, enc) for agg_id in range(2)]
-        (msgs, valid) = mastic.decide_batch(ctx, enc, shares[0][0], shares[1][0])
-        alive &= (valid == 1) & (shares[0][3] == 0) & (shares[1][3] == 0)
-        if mastic.JOINT_RAND_LEN > 0:
-            alive &= joint_rand_confirmed(msgs, shares[0][1], shares[1][1], n)
+    Round(mastic, ctx, verify_key)(dev, enc, alive, weight_check=True)
     mask = alive.astype(np.uint8)
     folds = [mastic.aggregate_grouped(agg_id, enc, ids, n_groups, mask, raw=fast) for agg_id in range(2)]
     counts = np.asarray(folds[0][1])
@@ -100,5 +84,5 @@ def compute_attribute_metrics(mastic: Mastic, ctx: bytes, attributes, reports, v
     for g in range(n_groups):
         pair = [folds[0][0][g], folds[1][0][g]]
         num = int(counts[g])
-        out.append((_unshard_raw(mastic, pair, num) if fast else mastic.unshard(agg_param, pair, num), num))
+        out.append((unshard_raw(mastic, pair, num) if fast else mastic.unshard(agg_param, pair, num), num))
     return out

@@ -26,13 +26,26 @@ MAX_GROUPS = 65536         # MASTIC_MAX_GROUPS
 CIRCUIT_IDS = {"Count": 1, "Sum": 2, "SumVec": 3, "Histogram": 4, "MultihotCountVec": 5}
 
 
-def _check(ctx_ptr, rc):
+def _check(ctx_ptr, rc, einval_is_value_error=True):
     if rc != 0:
         msg = _lib.lib().mastic_last_error(ctx_ptr) if ctx_ptr else b""
         text = (msg or b"").decode(errors="replace") or "mastic error"
-        if rc == -22:
+        if rc == -22 and einval_is_value_error:
             raise ValueError(text)
         raise _lib.MasticError(rc, text)
+
+
+def _previous(ctx_ptr, rc):
+    """A setter's return code: negative is an error, anything else the
+    previous setting."""
+    if rc < 0:
+        _check(ctx_ptr, rc)
+    return rc
+
+
+def _mask(valid):
+    """A per-report mask as the library takes it: contiguous uint8, or None."""
+    return None if valid is None else np.ascontiguousarray(np.asarray(valid, dtype=np.uint8))
 
 
 def _pack_path(path) -> bytes:
@@ -110,10 +123,7 @@ class Mastic:
         self.chunk_length = chunk_length
         self.vidpf = VidpfInfo(self.field, bits, sz.value_len)
         self._batch_n = [None, None]  # reports of each aggregator's last prep_init (aggregate_grouped's length check)
-        if circuit == "Sum":
-            self._wbits = max_measurement.bit_length()
-            self._offset = 2 ** self._wbits - 1 - max_measurement
-        elif circuit == "MultihotCountVec":
+        if circuit in ("Sum", "MultihotCountVec"):
             self._wbits = max_measurement.bit_length()
             self._offset = 2 ** self._wbits - 1 - max_measurement
 
@@ -196,7 +206,7 @@ class Mastic:
         """prep_init for n reports (wire in, wire out).  Returns
         (prep_shares bytes, jr_seeds bytes, out_shares bytes or None, status int32 array);
         status is 0 or a negative STATUS_* code (such a report is to be rejected)."""
-        enc = self.encode_agg_param(agg_param) if not isinstance(agg_param, (bytes, bytearray)) else bytes(agg_param)
+        enc = self._agg_param_bytes(agg_param)
         (level, count, wc) = self._agg_param_header(enc)
         n = len(nonces) // 16
         self._check_verify_key(verify_key)
@@ -204,11 +214,7 @@ class Mastic:
             raise ValueError("public shares have incorrect length")
         if len(input_shares) != n * self.sizes.input_share_size[agg_id]:
             raise ValueError("input shares have incorrect length")
-        ps = np.empty(n * self.prep_share_size(wc), np.uint8)
-        js = np.empty(n * 32, np.uint8)
-        ow = count * (1 + self.OUTPUT_LEN) * self.field.ENCODED_SIZE
-        out = np.empty(n * ow, np.uint8) if want_out_shares else None
-        st = np.empty(n, np.int32)
+        (ps, js, out, st) = self._prep_buffers(n, count, wc, want_out_shares)
         _check(self._ctx, _lib.lib().mastic_prep_init_batch(
             self._ctx, verify_key, len(verify_key), ctx, len(ctx), agg_id, enc, len(enc), n, _lib.buf(nonces),
             _lib.buf(public_shares), _lib.buf(input_shares), _lib.buf(ps), _lib.buf(js), _lib.buf(out),
@@ -216,9 +222,16 @@ class Mastic:
         self._batch_n[agg_id] = n
         return (ps.tobytes(), js.tobytes(), None if out is None else out.tobytes(), st)
 
+    def _prep_buffers(self, n: int, count: int, weight_check: bool, want_out_shares: bool):
+        """Host buffers for n reports' prep_init results at ``count`` candidates:
+        (prep shares, joint-rand seeds, out shares or None, status)."""
+        ow = count * (1 + self.OUTPUT_LEN) * self.field.ENCODED_SIZE
+        return (np.empty(n * self.prep_share_size(weight_check), np.uint8), np.empty(n * 32, np.uint8),
+                np.empty(n * ow, np.uint8) if want_out_shares else None, np.empty(n, np.int32))
+
     def decide_batch(self, ctx: bytes, agg_param, prep_shares_0: bytes, prep_shares_1: bytes):
         """prep_shares_to_prep for n report pairs -> (prep_msgs bytes, status uint8 array)."""
-        enc = self.encode_agg_param(agg_param) if not isinstance(agg_param, (bytes, bytearray)) else bytes(agg_param)
+        enc = self._agg_param_bytes(agg_param)
         (_level, _count, wc) = self._agg_param_header(enc)
         psz = self.prep_share_size(wc)
         n = len(prep_shares_0) // psz
@@ -249,9 +262,8 @@ class Mastic:
         (e.g. a torch tensor's ``data_ptr()``); the share stays in HBM.
         ``stream`` is the hipStream_t handle whose queued work last touched
         the buffer (0 = the null stream)."""
-        v = None if valid is None else np.ascontiguousarray(np.asarray(valid, dtype=np.uint8))
         _check(self._ctx, _lib.lib().mastic_aggregate_device_on_stream(
-            self._ctx, agg_id, _lib.buf(v), ctypes.c_void_p(dev_ptr), ctypes.c_void_p(stream or None)))
+            self._ctx, agg_id, _lib.buf(_mask(valid)), ctypes.c_void_p(dev_ptr), ctypes.c_void_p(stream or None)))
 
     # ------------------------------- multi-GPU merge (library-owned RCCL)
     @staticmethod
@@ -315,18 +327,17 @@ class Mastic:
         if zeros:
             mask |= 4  # MASTIC_MERGE_ZEROS
         out = np.empty(n_elems * self.field.ENCODED_SIZE, np.uint8)
-        v = None if valid is None else np.ascontiguousarray(np.asarray(valid, dtype=np.uint8))
-        _check(self._ctx, _lib.lib().mastic_aggregate_merged(self._ctx, mask, _lib.buf(v), n_elems, _lib.buf(out)))
+        _check(self._ctx, _lib.lib().mastic_aggregate_merged(self._ctx, mask, _lib.buf(_mask(valid)), n_elems,
+                                                             _lib.buf(out)))
         return out.tobytes()
 
     def aggregate_device(self, agg_id: int, agg_param, valid=None, raw=False):
         """Fold the out shares of the last prep_init(_batch) of agg_id on the GPU
         (raw=True: the agg share as encode_vec bytes, without decoding)."""
-        enc = self.encode_agg_param(agg_param) if not isinstance(agg_param, (bytes, bytearray)) else bytes(agg_param)
+        enc = self._agg_param_bytes(agg_param)
         (_level, count, _wc) = self._agg_param_header(enc)
         out = np.empty(count * (1 + self.OUTPUT_LEN) * self.field.ENCODED_SIZE, np.uint8)
-        v = None if valid is None else np.ascontiguousarray(np.asarray(valid, dtype=np.uint8))
-        _check(self._ctx, _lib.lib().mastic_aggregate(self._ctx, agg_id, _lib.buf(v), _lib.buf(out)))
+        _check(self._ctx, _lib.lib().mastic_aggregate(self._ctx, agg_id, _lib.buf(_mask(valid)), _lib.buf(out)))
         return out.tobytes() if raw else self.field.decode_vec(out.tobytes())
 
     def aggregate_grouped(self, agg_id: int, agg_param, groups, n_groups: int, valid=None, raw=False):
@@ -338,10 +349,10 @@ class Mastic:
         the list of the n_groups agg shares (bytes if ``raw``, else decoded
         field vectors), ``counts`` the uint64 array of reports folded into
         each (the buckets' ``num_measurements``)."""
-        enc = self.encode_agg_param(agg_param) if not isinstance(agg_param, (bytes, bytearray)) else bytes(agg_param)
+        enc = self._agg_param_bytes(agg_param)
         (_level, count, _wc) = self._agg_param_header(enc)
         g = np.ascontiguousarray(np.asarray(groups, dtype=np.uint32))
-        v = None if valid is None else np.ascontiguousarray(np.asarray(valid, dtype=np.uint8))
+        v = _mask(valid)
         share = count * (1 + self.OUTPUT_LEN) * self.field.ENCODED_SIZE
         n_groups = int(n_groups)
         if not 1 <= n_groups <= MAX_GROUPS:
@@ -370,14 +381,12 @@ class Mastic:
 
     def reports_upload(self, nonces: bytes, public_shares: bytes, input_shares_0=None, input_shares_1=None):
         rep = Reports(self, len(nonces) // 16)
-        _check(self._ctx, _lib.lib().mastic_reports_upload(
-            rep._ptr, _lib.buf(nonces), _lib.buf(public_shares), _lib.buf(input_shares_0),
-            _lib.buf(input_shares_1)))
+        rep.upload(nonces, public_shares, input_shares_0, input_shares_1)
         return rep
 
     def prep_init_device(self, reports, verify_key: bytes, ctx: bytes, agg_id: int, agg_param):
         """Enqueue prep_init for resident reports; results stay in HBM."""
-        enc = self.encode_agg_param(agg_param) if not isinstance(agg_param, (bytes, bytearray)) else bytes(agg_param)
+        enc = self._agg_param_bytes(agg_param)
         self._check_verify_key(verify_key)
         _check(self._ctx, _lib.lib().mastic_prep_init(self._ctx, reports._ptr, verify_key, len(verify_key), ctx,
                                                       len(ctx), agg_id, enc, len(enc)))
@@ -386,14 +395,9 @@ class Mastic:
     def prep_result(self, reports, agg_id: int, agg_param, want_out_shares=False):
         """Wire results of the last prep_init_device for agg_id:
         (prep_shares bytes, jr_seeds bytes, out_shares bytes or None, status int32 array)."""
-        enc = self.encode_agg_param(agg_param) if not isinstance(agg_param, (bytes, bytearray)) else bytes(agg_param)
+        enc = self._agg_param_bytes(agg_param)
         (_level, count, wc) = self._agg_param_header(enc)
-        n = reports.n
-        ps = np.empty(n * self.prep_share_size(wc), np.uint8)
-        js = np.empty(n * 32, np.uint8)
-        out = np.empty(n * count * (1 + self.OUTPUT_LEN) * self.field.ENCODED_SIZE, np.uint8) \
-            if want_out_shares else None
-        st = np.empty(n, np.int32)
+        (ps, js, out, st) = self._prep_buffers(reports.n, count, wc, want_out_shares)
         _check(self._ctx, _lib.lib().mastic_prep_result(self._ctx, agg_id, _lib.buf(ps), _lib.buf(js),
                                                         _lib.buf(out), _lib.buf(st)))
         return (ps.tobytes(), js.tobytes(), None if out is None else out.tobytes(), st)
@@ -419,7 +423,7 @@ class Mastic:
         return (v[0].value, k[0].value, v[1].value, k[1].value, v[2].value, k[2].value, v[3].value)
 
     def tree_stats(self, agg_param):
-        enc = self.encode_agg_param(agg_param) if not isinstance(agg_param, (bytes, bytearray)) else bytes(agg_param)
+        enc = self._agg_param_bytes(agg_param)
         a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
         _check(self._ctx, _lib.lib().mastic_tree_stats(self._ctx, enc, len(enc), ctypes.byref(a),
                                                        ctypes.byref(b), ctypes.byref(c)))
@@ -438,10 +442,7 @@ class Mastic:
         result / cache-slot allocations fail as if HBM were exhausted (the
         ENOMEM recovery path).  Outputs are identical either way.  Returns how
         many injected failures the previous setting had not yet used."""
-        rc = _lib.lib().mastic_set_test_hooks(self._ctx, int(force_slow_blk), int(fail_allocs))
-        if rc < 0:
-            _check(self._ctx, rc)
-        return rc
+        return _previous(self._ctx, _lib.lib().mastic_set_test_hooks(self._ctx, int(force_slow_blk), int(fail_allocs)))
 
     def set_test_sponge_delay(self, delay_us: int):
         """Test hook (``mastic_set_test_sponge_delay``): the next prep_init
@@ -457,10 +458,8 @@ class Mastic:
         the level kernel each by itself; False restores the overlapped
         schedule, None only queries.  Results are identical either way.
         Returns the previous setting."""
-        rc = _lib.lib().mastic_set_serial_sponges(self._ctx, -1 if on is None else int(bool(on)))
-        if rc < 0:
-            _check(self._ctx, rc)
-        return bool(rc)
+        return bool(_previous(self._ctx, _lib.lib().mastic_set_serial_sponges(
+            self._ctx, -1 if on is None else int(bool(on)))))
 
     def set_last_level_segments(self, k: int = 0) -> int:
         """Parent ranges of a prep_init's last level
@@ -468,10 +467,7 @@ class Mastic:
         forces k ranges (at most one per parent).  Only calls with no frontier
         cache that run as one stream of chunks are segmented.  Results are
         identical for every k.  Returns the previous setting."""
-        rc = _lib.lib().mastic_set_last_level_segments(self._ctx, int(k))
-        if rc < 0:
-            _check(self._ctx, rc)
-        return rc
+        return _previous(self._ctx, _lib.lib().mastic_set_last_level_segments(self._ctx, int(k)))
 
     def set_frontier_cache(self, on: bool):
         """Keep each prep_init's per-level binder inputs and last frontier in HBM so
@@ -498,20 +494,16 @@ class Mastic:
         mode."""
         if mode is not None and mode not in self.CACHE_NODES:
             raise ValueError("cache nodes mode must be one of %s" % (self.CACHE_NODES,))
-        rc = _lib.lib().mastic_set_frontier_cache_nodes(
-            self._ctx, -1 if mode is None else self.CACHE_NODES.index(mode), None, None)
-        if rc < 0:
-            _check(self._ctx, rc)
-        return self.CACHE_NODES[rc]
+        return self.CACHE_NODES[_previous(self._ctx, _lib.lib().mastic_set_frontier_cache_nodes(
+            self._ctx, -1 if mode is None else self.CACHE_NODES.index(mode), None, None))]
 
     def last_cache_nodes(self):
         """``(in, out)`` of the last prep_init: the node format its cache hit
         read and the format it wrote into the cache, each ``'seeds'``,
         ``'payloads'`` or None (not a hit / nothing written)."""
         vin, vout = ctypes.c_int(), ctypes.c_int()
-        rc = _lib.lib().mastic_set_frontier_cache_nodes(self._ctx, -1, ctypes.byref(vin), ctypes.byref(vout))
-        if rc < 0:
-            _check(self._ctx, rc)
+        _previous(self._ctx, _lib.lib().mastic_set_frontier_cache_nodes(self._ctx, -1, ctypes.byref(vin),
+                                                                        ctypes.byref(vout)))
         return tuple(None if v.value < 0 else self.CACHE_NODES[v.value] for v in (vin, vout))
 
     def proof_tree(self, agg_id: int, ctx: bytes, n: int):
@@ -532,7 +524,7 @@ class Mastic:
     def work_bytes(self, agg_param):
         """HBM work bytes per report of one prep_init at this agg param
         (batches larger than the memory budget allows are run in chunks)."""
-        enc = self.encode_agg_param(agg_param) if not isinstance(agg_param, (bytes, bytearray)) else bytes(agg_param)
+        enc = self._agg_param_bytes(agg_param)
         v = ctypes.c_uint64()
         _check(self._ctx, _lib.lib().mastic_work_bytes(self._ctx, enc, len(enc), ctypes.byref(v)))
         return v.value
@@ -546,6 +538,10 @@ class Mastic:
             raise TypeError("verify key must be bytes")
         if len(verify_key) > 255:
             raise ValueError("verify key has incorrect length")
+
+    def _agg_param_bytes(self, agg_param) -> bytes:
+        """The batch calls take an aggregation parameter as the tuple or encoded."""
+        return bytes(agg_param) if isinstance(agg_param, (bytes, bytearray)) else self.encode_agg_param(agg_param)
 
     @staticmethod
     def _agg_param_header(enc: bytes):
@@ -794,10 +790,9 @@ class Reports:
         if k is not None and k.shape != (self.n,):
             raise ValueError("keep must have one entry per report")
         kept = ctypes.c_size_t()
-        rc = _lib.lib().mastic_reports_compact(self._ptr, _lib.buf(k), staging_bytes, ctypes.byref(kept))
-        if rc != 0:  # MasticError for every code: a view or a missing mask is EINVAL, not a bad value
-            msg = _lib.lib().mastic_last_error(self._m._ctx)
-            raise _lib.MasticError(rc, (msg or b"").decode(errors="replace") or "mastic error")
+        # MasticError for every code: a view or a missing mask is EINVAL, not a bad value
+        _check(self._m._ctx, _lib.lib().mastic_reports_compact(self._ptr, _lib.buf(k), staging_bytes,
+                                                               ctypes.byref(kept)), einval_is_value_error=False)
         self.n = kept.value
         return self.n
 
