@@ -28,6 +28,9 @@
 //                  agg_update / merge over reports (:379-397)
 //   k_decide       decide_kernels.hpp
 //                  prep_shares_to_prep (:320-362)
+//   k_decide_peer  decide_kernels.hpp
+//                  prep_shares_to_prep + one aggregator's prep_next (:320-377),
+//                  its own result planes against the peer's wire prep shares
 // Without a counterpart in the reference: the wire unpacking and key setup
 // (unpack_kernels.hpp), the prefix states (planes.hpp), the convert streams'
 // buffering (conv_stream.hpp).  The client's k_shard is shard.hpp's, outside

@@ -43,6 +43,7 @@ static_assert(SCHED_EVAL_WAVES == EVAL_WAVES && SCHED_EVAL_PROOF_WAVES == EVAL_P
 
 #include "ctx.hpp"
 #include "prep.hpp"
+#include "peer.hpp"
 #include "fold.hpp"
 #include "comm.hpp"
 #include "reports.hpp"

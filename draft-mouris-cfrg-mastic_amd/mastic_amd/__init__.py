@@ -9,4 +9,5 @@ from .field import Field64, Field128  # noqa: F401
 from .nonce_set import NonceSet  # noqa: F401
 from .vdaf import (NO_GROUP, Mastic, MasticCount, MasticHistogram, MasticMultihotCountVec,  # noqa: F401
                    MasticSum, MasticSumVec, from_test_vec)
+from .aggregator import Aggregator  # noqa: F401,E402
 from . import metrics  # noqa: F401,E402

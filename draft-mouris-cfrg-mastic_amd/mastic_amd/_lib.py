@@ -41,7 +41,7 @@ EXPORTS = [
     "mastic_allgather_fold", "mastic_aggregate_merged", "mastic_merge_host",
     "mastic_nonce_set_create", "mastic_nonce_set_destroy", "mastic_nonce_set_count", "mastic_nonce_set_admit",
     "mastic_nonce_set_admit_reports", "mastic_nonce_set_contains", "mastic_nonce_set_export",
-    "mastic_reports_compact", "mastic_aggregate_grouped",
+    "mastic_reports_compact", "mastic_aggregate_grouped", "mastic_decide_peer",
 ]
 COMM_ID_BYTES = 128  # MASTIC_COMM_ID_BYTES (= RCCL's NCCL_UNIQUE_ID_BYTES)
 ROCM_PATH = "/opt/rocm"  # the image's ROCm (the library dlopens librccl.so.1 from its lib/ on first comm use)
@@ -168,6 +168,7 @@ def lib():
                     "mastic_set_last_level_segments": (i32, [P, i32]),
                     "mastic_reports_view": (i32, [P, sz, sz, ctypes.POINTER(P)]),
                     "mastic_decide_results": (i32, [P, u8p, sz, P, P]),
+                    "mastic_decide_peer": (i32, [P, i32, u8p, sz, P, P, sz, P, P, P]),
                     "mastic_last_timing3": (i32, [P] + [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)] * 3
                                             + [ctypes.POINTER(ctypes.c_double)]),
                     "mastic_work_bytes": (i32, [P, u8p, sz, ctypes.POINTER(ctypes.c_uint64)]),

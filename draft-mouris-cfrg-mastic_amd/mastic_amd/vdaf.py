@@ -21,6 +21,11 @@ PROOF_SIZE = 32
 STATUS_OK = 0
 STATUS_QUERY_ABORT = -2    # FlpBBCGGI19.query: the test point is a root of unity
 STATUS_NONCANONICAL = -3   # a wire field element (payload correction word, leader proof share) is >= p
+# per-report codes of decide_batch / decide_results / decide_peer (MASTIC_DECIDE_*)
+DECIDE_VIDPF_FAIL = 0
+DECIDE_OK = 1
+DECIDE_FLP_FAIL = 2
+DECIDE_SKIPPED = 3         # decide_peer: no check ran (own status nonzero, or the peer did not offer the report)
 NO_GROUP = 0xFFFFFFFF      # MASTIC_GROUP_NONE: a report of aggregate_grouped that belongs to no bucket
 MAX_GROUPS = 65536         # MASTIC_MAX_GROUPS
 CIRCUIT_IDS = {"Count": 1, "Sum": 2, "SumVec": 3, "Histogram": 4, "MultihotCountVec": 5}
@@ -123,6 +128,7 @@ class Mastic:
         self.chunk_length = chunk_length
         self.vidpf = VidpfInfo(self.field, bits, sz.value_len)
         self._batch_n = [None, None]  # reports of each aggregator's last prep_init (aggregate_grouped's length check)
+        self._batch_wc = [False, False]  # and whether it had the weight check (decide_peer's prep share size)
         if circuit in ("Sum", "MultihotCountVec"):
             self._wbits = max_measurement.bit_length()
             self._offset = 2 ** self._wbits - 1 - max_measurement
@@ -219,7 +225,7 @@ class Mastic:
             self._ctx, verify_key, len(verify_key), ctx, len(ctx), agg_id, enc, len(enc), n, _lib.buf(nonces),
             _lib.buf(public_shares), _lib.buf(input_shares), _lib.buf(ps), _lib.buf(js), _lib.buf(out),
             _lib.buf(st)))
-        self._batch_n[agg_id] = n
+        (self._batch_n[agg_id], self._batch_wc[agg_id]) = (n, wc)
         return (ps.tobytes(), js.tobytes(), None if out is None else out.tobytes(), st)
 
     def _prep_buffers(self, n: int, count: int, weight_check: bool, want_out_shares: bool):
@@ -252,6 +258,36 @@ class Mastic:
         code = np.empty(n, np.uint8)
         _check(self._ctx, _lib.lib().mastic_decide_results(self._ctx, ctx, len(ctx), _lib.buf(acc), _lib.buf(code)))
         return (acc, code)
+
+    def decide_peer(self, agg_id: int, ctx: bytes, peer_prep_shares: bytes, peer_ok=None):
+        """One aggregator of two (``mastic_decide_peer``): prep_shares_to_prep
+        plus this aggregator's prep_next for the last prep_init_device of
+        ``agg_id``, against the other aggregator's wire prep shares for the
+        same reports and agg param; the own prep shares stay in HBM.
+        ``peer_ok[i]`` (None: all) says whether the peer offers report i.
+        Returns ``(accept, codes, prep_msgs)``: uint8 arrays of one entry per
+        report (codes: 0 VIDPF fail, 1 OK, 2 FLP fail, :data:`DECIDE_SKIPPED`)
+        and the 32-byte prep messages as a uint8 array, None unless the call
+        had the weight check and the circuit joint randomness."""
+        if agg_id not in (0, 1) or self._batch_n[agg_id] is None:
+            raise ValueError("no prep_init result for this aggregator" if agg_id in (0, 1) else "invalid aggregator ID")
+        # _batch_wc shadows the result slot's weight_check: prep_init_batch and prep_init_device, which set it,
+        # are the only callers of mastic_prep_init*, so the two cannot drift
+        wc = self._batch_wc[agg_id]
+        # the library reads n * prep_share_size bytes: the lengths are checked here
+        rows = np.frombuffer(peer_prep_shares, np.uint8)  # bytes or a contiguous array, not copied
+        if rows.size % self.prep_share_size(wc):
+            raise ValueError("peer prep shares have incorrect length")
+        n_peer = rows.size // self.prep_share_size(wc)
+        ok = _mask(peer_ok)
+        if ok is not None and ok.shape != (n_peer,):
+            raise ValueError("peer_ok has %d entries, the peer's prep shares are for %d reports" % (ok.size, n_peer))
+        acc = np.zeros(n_peer, np.uint8)
+        code = np.zeros(n_peer, np.uint8)
+        msgs = np.zeros(32 * n_peer, np.uint8) if wc and self.JOINT_RAND_LEN > 0 else None
+        _check(self._ctx, _lib.lib().mastic_decide_peer(self._ctx, agg_id, ctx, len(ctx), _lib.buf(rows), _lib.buf(ok),
+                                                        n_peer, _lib.buf(acc), _lib.buf(code), _lib.buf(msgs)))
+        return (acc, code, msgs)
 
     def select_timing(self, agg_id: int):
         """Make last_timing* report agg_id's last prep_init (waits for it)."""
@@ -390,17 +426,21 @@ class Mastic:
         self._check_verify_key(verify_key)
         _check(self._ctx, _lib.lib().mastic_prep_init(self._ctx, reports._ptr, verify_key, len(verify_key), ctx,
                                                       len(ctx), agg_id, enc, len(enc)))
-        self._batch_n[agg_id] = reports.n
+        (self._batch_n[agg_id], self._batch_wc[agg_id]) = (reports.n, self._agg_param_header(enc)[2])
 
-    def prep_result(self, reports, agg_id: int, agg_param, want_out_shares=False):
+    def prep_result(self, reports, agg_id: int, agg_param, want_out_shares=False, want_jr_seeds=True):
         """Wire results of the last prep_init_device for agg_id:
-        (prep_shares bytes, jr_seeds bytes, out_shares bytes or None, status int32 array)."""
+        (prep_shares bytes, jr_seeds bytes or None, out_shares bytes or None, status int32 array).
+        ``want_jr_seeds=False`` leaves the joint-rand seeds in HBM (an aggregator that decides with
+        :meth:`decide_peer` never needs them on the host)."""
         enc = self._agg_param_bytes(agg_param)
         (_level, count, wc) = self._agg_param_header(enc)
         (ps, js, out, st) = self._prep_buffers(reports.n, count, wc, want_out_shares)
+        if not want_jr_seeds:
+            js = None
         _check(self._ctx, _lib.lib().mastic_prep_result(self._ctx, agg_id, _lib.buf(ps), _lib.buf(js),
                                                         _lib.buf(out), _lib.buf(st)))
-        return (ps.tobytes(), js.tobytes(), None if out is None else out.tobytes(), st)
+        return (ps.tobytes(), None if js is None else js.tobytes(), None if out is None else out.tobytes(), st)
 
     def synchronize(self):
         _check(self._ctx, _lib.lib().mastic_synchronize(self._ctx))

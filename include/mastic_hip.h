@@ -486,6 +486,34 @@ int mastic_decide_batch(mastic_ctx* ctx, const uint8_t* app_ctx, size_t ctx_len,
                         size_t agg_param_len, size_t n, const uint8_t* prep_shares0, const uint8_t* prep_shares1,
                         uint8_t* prep_msgs_out, uint8_t* valid_out);
 
+/* One aggregator of two: prep_shares_to_prep plus this aggregator's prep_next
+ * (mastic.py:320-377) for the last mastic_prep_init of agg_id on this ctx,
+ * against the other aggregator's prep shares for the same reports and agg
+ * param.  This aggregator's prep shares, joint-rand seeds and status are read
+ * where they lie in HBM and never leave it; the other aggregator's result slot
+ * of the ctx (a ctx may hold both) is not touched.
+ * peer_prep_shares: host memory, n*prep_share_size[weight_check of the result]
+ * bytes in wire encoding (mastic.py:543-552).  peer_ok (n bytes, NULL = all):
+ * nonzero iff the peer offers report i.  n must be the result's n
+ * (MASTIC_EINVAL otherwise, as for an agg_id that is not 0 or 1 or has no
+ * result).
+ * decide_out[i] = MASTIC_DECIDE_SKIPPED if this aggregator's status of report
+ * i is nonzero or peer_ok[i] == 0; else the MASTIC_DECIDE_* code of
+ * mastic_decide_batch for (aggregator 0's share, aggregator 1's share): the
+ * joint-rand seed absorbs aggregator 0's part first whichever side calls, and
+ * a non-canonical verifier element gives MASTIC_DECIDE_FLP_FAIL.
+ * accept_out[i] = 1 iff the code is MASTIC_DECIDE_OK and (weight check with
+ * joint randomness) the prep message equals this aggregator's own joint-rand
+ * seed.  prep_msgs_out (n*32) is written when the result has the weight check
+ * and the circuit joint randomness, as mastic_decide_batch writes it, with
+ * zeros for skipped and failed reports; otherwise it is untouched.  Every
+ * output may be NULL.  Blocks; runs on the ctx's main stream after the queued
+ * prep_init. */
+#define MASTIC_DECIDE_SKIPPED 3 /* no check ran: own status != 0, or the peer did not offer the report */
+int mastic_decide_peer(mastic_ctx* ctx, int agg_id, const uint8_t* app_ctx, size_t ctx_len,
+                       const uint8_t* peer_prep_shares, const uint8_t* peer_ok, size_t n, uint8_t* accept_out,
+                       uint8_t* decide_out, uint8_t* prep_msgs_out);
+
 /* One-shot client shard of n reports into host buffers. */
 int mastic_shard_batch(mastic_ctx* ctx, const uint8_t* app_ctx, size_t ctx_len, size_t n, const uint8_t* alphas,
                        const uint8_t* betas, const uint8_t* nonces, const uint8_t* rands, uint8_t* public_shares_out,
